@@ -25,6 +25,12 @@ checks the N-rank residual and J.v of a 16^3 cavity (same transport) against a s
 rank 0 (abort above 1e-12; `preflight_relerr`). Fixed total problem -> "scaling": "strong"; value =
 nonlinear iterations/s of the whole job; `rccl_ranks` = the in-library communicator's size as RCCL
 reports it, `devices` = distinct GPUs behind the ranks.
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, ms_per_step, the
+solver's counts). --full adds what takes runs of its own after the timed steps: the per-kernel breakdown of one
+instrumented step, the J.v roofline (back-to-back launches, HBM-traffic counter passes, LDS model), the whole-step
+roofline and the CPU baseline. --dump-outputs DIR writes the last timed step's iterate and solver counts
+(dump_outputs) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -166,6 +172,30 @@ def step_bytes_model(n, k, m, L, f32_fine, k_hist=2):
              "jacobi_first_sweeps": vcyc * sum(24 * sz(c)[1] for c in levels[:-1]),
              "orthogonalisation": 8 * N * (sum(2 * j + 3 for j in range(1, int(m) + 1)) + int(m) + 2)}
     return sum(parts.values()), parts
+
+
+DUMP_MAX_BYTES = 32 << 20   # of the dumped iterate over all ranks; a run's files stay far below 64 MB
+
+
+def dump_outputs(path, present, stats, rank=0, world=1):
+    """--dump-outputs: what the last timed step handed back to its caller, as float64 arrays under `path`:
+    present.npy -- the Newton iterate the step left in `present` (whole while it fits DUMP_MAX_BYTES, else its
+    entries at a fixed, seeded sample of indices in ascending order) -- and newton_stats.npy = the step's
+    [newton_iterations, linear_iterations, residual_evaluations, final_residual, linear_failures]. The state
+    every step starts from is synthetic and fixed, so two builds run with the same arguments are comparable
+    entry for entry. On N ranks each writes its local vector's share as <name>_rank<r>.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n, cap = present.numel(), DUMP_MAX_BYTES // 8 // world
+    x = present
+    if n > cap:
+        idx = np.sort(np.random.default_rng(20200200).integers(0, n, cap))
+        x = present[torch.from_numpy(idx).to(present.device)]
+    tag = "_rank%d" % rank if world > 1 else ""
+    np.save(os.path.join(path, "present%s.npy" % tag), x.detach().cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "newton_stats%s.npy" % tag),
+            np.array([stats[key] for key in ("newton_iterations", "linear_iterations", "residual_evaluations",
+                                             "final_residual", "linear_failures")], dtype=np.float64))
 
 
 def _cpu_model():
@@ -418,24 +448,31 @@ def bench_cylinder3d(args):
     stats = [one_step() for _ in range(args.steps)]
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    ctx.set_state(present, m1, m2)
-    v = torch.rand(ctx.n_dofs, dtype=torch.float64, device=dev)
-    y = torch.empty_like(v)
-    ctx.jacobian_apply(v, y)
-    ctx.timing(True)
-    for _ in range(args.jv_reps):
-        ctx.jacobian_apply(v, y)
-    jv_ms, jv_n = ctx.timing_get(1)
-    ctx.timing(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, present, stats[-1])
     N, nc = ctx.n_dofs, sp["n_cells"]
-    # algorithmic bytes of one per-cell J.v launch (gls_cell_kernel MODE_JV, element-vector output):
-    # v and the linearization state u (8N each; the GLS Jacobian needs the full strong residual of u,
-    # p), the cell node maps (4 B x (27 + 8) per cell), the MappingQ geometry per quadrature point
-    # (22 doubles: x_q, JxW, J^-1, G = J^-1 J^-T, the Hessian correction -- FEValues' per-q data) and
-    # the element vectors written (8 B x (3 x 27 + 8) per cell; summed into Jv by the gather kernel)
-    B = 16 * N + 4 * nc * (27 + 8) + 22 * 8 * 27 * nc + 8 * nc * (3 * 27 + 8)
-    ms = jv_ms / max(jv_n, 1)
     its_per_s = args.steps / el
+    roofline = None
+    if args.full:  # back-to-back J.v launches on the step's state for the per-cell kernel's roofline
+        ctx.set_state(present, m1, m2)
+        v = torch.rand(ctx.n_dofs, dtype=torch.float64, device=dev)
+        y = torch.empty_like(v)
+        ctx.jacobian_apply(v, y)
+        ctx.timing(True)
+        for _ in range(args.jv_reps):
+            ctx.jacobian_apply(v, y)
+        jv_ms, jv_n = ctx.timing_get(1)
+        ctx.timing(False)
+        # algorithmic bytes of one per-cell J.v launch (gls_cell_kernel MODE_JV, element-vector output):
+        # v and the linearization state u (8N each; the GLS Jacobian needs the full strong residual of u,
+        # p), the cell node maps (4 B x (27 + 8) per cell), the MappingQ geometry per quadrature point
+        # (22 doubles: x_q, JxW, J^-1, G = J^-1 J^-T, the Hessian correction -- FEValues' per-q data) and
+        # the element vectors written (8 B x (3 x 27 + 8) per cell; summed into Jv by the gather kernel)
+        B = 16 * N + 4 * nc * (27 + 8) + 22 * 8 * 27 * nc + 8 * nc * (3 * 27 + 8)
+        ms = jv_ms / max(jv_n, 1)
+        roofline = {"bound": "hbm", "kernel": cell_jv_kernel_name(1), "achieved": B / (ms * 1e-3) / 1e9,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": B / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
+                    "algorithmic_bytes_per_launch": B, "launch_ms": ms}
     out = {
         "metric": ("nonlinear iters/sec (3D Taylor-Couette, Q2-Q1 mapped, steady)" if tc else
                    "nonlinear iters/sec (3D cylinder Re 200, Q2-Q1 mapped, BDF2)"), "value": its_per_s,
@@ -464,10 +501,10 @@ def bench_cylinder3d(args):
         "setup_s": t_setup,
         "mdof_per_s": N * its_per_s / 1e6,
         "linear_iterations_per_step": float(np.mean([s_["linear_iterations"] for s_ in stats])),
-        "roofline": {"bound": "hbm", "kernel": cell_jv_kernel_name(1), "achieved": B / (ms * 1e-3) / 1e9,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": B / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
-                     "algorithmic_bytes_per_launch": B, "launch_ms": ms},
+        "full": bool(args.full),
     }
+    if roofline:
+        out["roofline"] = roofline
     print(json.dumps(out))
 
 
@@ -511,22 +548,31 @@ def bench_octree(args):
     stats = [one_step() for _ in range(args.steps)]
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    ctx.set_state(present, m1, m2)
-    v = torch.rand(ctx.n_dofs, dtype=torch.float64, device=dev)
-    y = torch.empty_like(v)
-    ctx.jacobian_apply(v, y)
-    ctx.timing(True)
-    for _ in range(args.jv_reps):
-        ctx.jacobian_apply(v, y)
-    jv_ms, jv_n = ctx.timing_get(1)
-    ctx.timing(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, present, stats[-1])
     N, nc = ctx.n_dofs, prob.mesh["n_cells"]
-    # algorithmic bytes of one J.v (the sibling-group bricks on the pencil kernel, the other leaves on the
-    # per-cell kernel, both writing element vectors summed per node): v and u (8N each), node maps
-    # (4 B x 2 x 27 per cell), the cell box (48 B), the element vectors (8 B x 4 x 27)
-    B = 16 * N + 4 * nc * 54 + 48 * nc + 8 * nc * 4 * 27
-    ms = jv_ms / max(jv_n, 1)
     its_per_s = args.steps / el
+    roofline = None
+    if args.full:  # back-to-back J.v launches on the step's state for the roofline
+        ctx.set_state(present, m1, m2)
+        v = torch.rand(ctx.n_dofs, dtype=torch.float64, device=dev)
+        y = torch.empty_like(v)
+        ctx.jacobian_apply(v, y)
+        ctx.timing(True)
+        for _ in range(args.jv_reps):
+            ctx.jacobian_apply(v, y)
+        jv_ms, jv_n = ctx.timing_get(1)
+        ctx.timing(False)
+        # algorithmic bytes of one J.v (the sibling-group bricks on the pencil kernel, the other leaves on the
+        # per-cell kernel, both writing element vectors summed per node): v and u (8N each), node maps
+        # (4 B x 2 x 27 per cell), the cell box (48 B), the element vectors (8 B x 4 x 27)
+        B = 16 * N + 4 * nc * 54 + 48 * nc + 8 * nc * 4 * 27
+        ms = jv_ms / max(jv_n, 1)
+        roofline = {"bound": "hbm", "kernel": "gls_pencil_kernel<double,MODE_JVQ> (sibling-group bricks) + "
+                                              "%s (other leaves) + k_gather_ev" % cell_jv_kernel_name(2),
+                    "achieved": B / (ms * 1e-3) / 1e9,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": B / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
+                    "algorithmic_bytes_per_launch": B, "launch_ms": ms}
     lev = [int(v_) for v_ in np.bincount(prob.mesh["cell_level"])]
     out = {
         "metric": "nonlinear iters/sec (3D lid-driven cavity, adapted octree, Q%d-Q%d, BDF2)" % (args.k, args.kp),
@@ -547,12 +593,10 @@ def bench_octree(args):
         "mdof_per_s": N * its_per_s / 1e6,
         "linear_iterations_per_step": float(np.mean([s_["linear_iterations"] for s_ in stats])),
         "forest_bricks": ctx.forest_bricks(),
-        "roofline": {"bound": "hbm", "kernel": "gls_pencil_kernel<double,MODE_JVQ> (sibling-group bricks) + "
-                                               "%s (other leaves) + k_gather_ev" % cell_jv_kernel_name(2),
-                     "achieved": B / (ms * 1e-3) / 1e9,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": B / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
-                     "algorithmic_bytes_per_launch": B, "launch_ms": ms},
+        "full": bool(args.full),
     }
+    if roofline:
+        out["roofline"] = roofline
     print(json.dumps(out))
 
 
@@ -700,8 +744,14 @@ def main():
     ap.add_argument("--workload", default="cavity", choices=["cavity", "cylinder3d", "taylorcouette3d", "octree"],
                     help="cavity: the BASELINE metric (configs[1] / [2]); cylinder3d: configs[4]'s adaptive-path "
                          "problem on one GPU (per-cell mapped kernels + ILU-GMRES)")
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the per-kernel "
+                         "breakdown (one instrumented step), the J.v roofline launches, the HBM-traffic PMC passes, the "
+                         "LDS model and the CPU baseline (--no-cpu, --cpu-full, --no-pmc, --jv-reps act only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--cells", dest="n", type=int, default=128, help="cells per direction")
     ap.add_argument("--k", type=int, default=2)
     ap.add_argument("--kp", type=int, default=2)
@@ -785,6 +835,8 @@ def main():
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if env_world is not None and int(env_world) != args.gpus:
         sys.stderr.write("bench.py: WORLD_SIZE=%s but --gpus %d: launch one rank per GPU (torch.distributed.run "
                          "--nproc-per-node %d ... --gpus %d) or run without a launcher\n"
@@ -946,62 +998,18 @@ def main():
     barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    # per-kernel breakdown: one extra, instrumented step (HIP events around every launch)
-    ctx.timing(True)
-    tb0 = time.perf_counter()
-    one_step()
-    torch.cuda.synchronize()
-    elapsed_instr = time.perf_counter() - tb0
-    jv_ms, jv_n = ctx.timing_get(1)
-    res_ms, res_n = ctx.timing_get(0)
-    dg_ms, dg_n = ctx.timing_get(2)
-    lin_ms, lin_n = ctx.timing_get(3)
-    f32_ms, f32_n = ctx.timing_get(4)
-    sl_ms, sl_n = ctx.timing_get(5)
-    ctx.timing(False)
-    # dedicated back-to-back J.v launches on the same state for a clean per-launch duration
-    ctx.set_state(present, m1, m2)
-    v = torch.rand(N, dtype=torch.float64, device=dev)
-    y = torch.empty_like(v)
-    ctx.jacobian_apply(v, y)
-    ctx.timing(True)
-    for _ in range(args.jv_reps):
-        ctx.jacobian_apply(v, y)
-    jv2_ms, jv2_n = ctx.timing_get(1)
-    sl2_ms, sl2_n = ctx.timing_get(5)
-    ctx.timing(False)
-
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, present, stats[-1], rank, world)
     t_max = elapsed
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64)
         tt = tt.to(dev) if args.dist_backend == "nccl" else tt
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         t_max = float(tt.item())
-
     lin_its = [s["linear_iterations"] for s in stats]
     nres = [s["residual_evaluations"] for s in stats]
     its_per_s = args.steps / t_max  # the whole job advances one Newton iteration per step
     n_cells = mesh["n_cells"]
-    nv = mesh["n_vnodes"]
-    nvdofs = 3 * nv
-    # algorithmic bytes of one J.v launch (SURVEY §8d, this build's layout): v, Jv, u (8N each),
-    # 2 history velocity vectors (BDF2), cell->node int32 indices, per-cell geometry (4 doubles),
-    # velocity constraint mask (1 B/node)
-    nvl = (args.k + 1) ** 3
-    n_cells_rank = n_cells // world
-    nv_rank = (N // 4) if world > 1 else nv
-    k_hist = 2 if args.scheme == "bdf2" else 0  # history vectors the scheme reads
-    B_jv = 8 * N * 3 + 8 * k_hist * 3 * nv_rank + 4 * n_cells_rank * nvl * (1 if args.kp == args.k else 2) + \
-        32 * n_cells_rank + nv_rank
-    jv_launch_ms = jv2_ms / max(jv2_n, 1)
-    # the brick kernel writes per-brick surface slabs; the deterministic node sum (k_slab_sum) that
-    # turns them into y is part of the same J.v, so its time is charged to the J.v's bytes too
-    slab_launch_ms = sl2_ms / max(jv2_n, 1)
-    op_ms = jv_launch_ms + slab_launch_ms
-    achieved = B_jv / (op_ms * 1e-3) / 1e9
-    pencil = os.environ.get("GLS_PENCIL", "1") != "0"
-    pencil_jv = pencil and args.k == 2  # the Q2 brick J.v runs in the pencil dataflow (gls_brick_pencil.hip)
-    # dense-contraction FLOP count of the kernel as written (per cell, Q2-Q2 3D): see DESIGN.md §4
     out = {
         "metric": "nonlinear iters/sec (3D cavity Q%d %d^3 %s)" % (args.k, args.n, args.scheme.upper()),
         "value": its_per_s,
@@ -1038,6 +1046,61 @@ def main():
         "dist_impl_fallback": getattr(args, "dist_impl_fallback", None),
         "linear_iterations_per_step": float(np.mean(lin_its)),
         "residual_evaluations_per_step": float(np.mean(nres)),
+        "setup_s": t_setup,
+        "full": bool(args.full),
+    }
+    if not args.full:  # the headline figure needs nothing more
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    # per-kernel breakdown: one extra, instrumented step (HIP events around every launch)
+    ctx.timing(True)
+    tb0 = time.perf_counter()
+    one_step()
+    torch.cuda.synchronize()
+    elapsed_instr = time.perf_counter() - tb0
+    jv_ms, jv_n = ctx.timing_get(1)
+    res_ms, res_n = ctx.timing_get(0)
+    dg_ms, dg_n = ctx.timing_get(2)
+    lin_ms, lin_n = ctx.timing_get(3)
+    f32_ms, f32_n = ctx.timing_get(4)
+    sl_ms, sl_n = ctx.timing_get(5)
+    ctx.timing(False)
+    # dedicated back-to-back J.v launches on the same state for a clean per-launch duration
+    ctx.set_state(present, m1, m2)
+    v = torch.rand(N, dtype=torch.float64, device=dev)
+    y = torch.empty_like(v)
+    ctx.jacobian_apply(v, y)
+    ctx.timing(True)
+    for _ in range(args.jv_reps):
+        ctx.jacobian_apply(v, y)
+    jv2_ms, jv2_n = ctx.timing_get(1)
+    sl2_ms, sl2_n = ctx.timing_get(5)
+    ctx.timing(False)
+
+    nv = mesh["n_vnodes"]
+    nvdofs = 3 * nv
+    # algorithmic bytes of one J.v launch (SURVEY §8d, this build's layout): v, Jv, u (8N each),
+    # 2 history velocity vectors (BDF2), cell->node int32 indices, per-cell geometry (4 doubles),
+    # velocity constraint mask (1 B/node)
+    nvl = (args.k + 1) ** 3
+    n_cells_rank = n_cells // world
+    nv_rank = (N // 4) if world > 1 else nv
+    k_hist = 2 if args.scheme == "bdf2" else 0  # history vectors the scheme reads
+    B_jv = 8 * N * 3 + 8 * k_hist * 3 * nv_rank + 4 * n_cells_rank * nvl * (1 if args.kp == args.k else 2) + \
+        32 * n_cells_rank + nv_rank
+    jv_launch_ms = jv2_ms / max(jv2_n, 1)
+    # the brick kernel writes per-brick surface slabs; the deterministic node sum (k_slab_sum) that
+    # turns them into y is part of the same J.v, so its time is charged to the J.v's bytes too
+    slab_launch_ms = sl2_ms / max(jv2_n, 1)
+    op_ms = jv_launch_ms + slab_launch_ms
+    achieved = B_jv / (op_ms * 1e-3) / 1e9
+    pencil = os.environ.get("GLS_PENCIL", "1") != "0"
+    pencil_jv = pencil and args.k == 2  # the Q2 brick J.v runs in the pencil dataflow (gls_brick_pencil.hip)
+    # dense-contraction FLOP count of the kernel as written (per cell, Q2-Q2 3D): see DESIGN.md §4
+    out.update({
         "kernel_ms": {"jacobian_apply": jv_ms / max(jv_n, 1), "residual": res_ms / max(res_n, 1),
                       "diagonal": dg_ms / max(dg_n, 1), "jv_linearization": lin_ms / max(lin_n, 1),
                       "smoother_jv_f32": f32_ms / max(f32_n, 1), "slab_sum": sl_ms / max(sl_n, 1),
@@ -1062,8 +1125,7 @@ def main():
                      "traffic": None, "algorithmic_bytes_per_launch": B_jv, "launch_ms": op_ms,
                      "launch_ms_by_kernel": {"gls_pencil_kernel" if pencil_jv else "gls_brick_kernel": jv_launch_ms,
                                              "k_slab_sum": slab_launch_ms}},
-        "setup_s": t_setup,
-    }
+    })
     # the whole Newton iteration against the HBM roof: algorithmic bytes of every operator / vector pass of the
     # step (model, step_bytes_model) over the measured step time
     if world == 1 and ctx.uses_brick_kernels and args.precond == "mg" and args.scheme == "bdf2":

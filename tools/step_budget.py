@@ -1,7 +1,8 @@
 """Per-Newton-step budget of the configs[2] bench by kernel class (tooling, not product code).
 
-Inputs: a rocprofv3 --kernel-trace CSV of `bench.py` (Q2-Q2 n^3 BDF2) and, optionally, the counter CSVs of two
-separate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` runs of `bench.py --steps 1 --warmup 0`.
+Inputs: a rocprofv3 --kernel-trace CSV of `bench.py --full --no-cpu --no-pmc` (Q2-Q2 n^3 BDF2) and, optionally,
+the counter CSVs of two separate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` runs of
+`bench.py --full --no-cpu --no-pmc --steps 1 --warmup 0` (--full: the instrumented step closes the trace).
 A Newton step starts at the fused residual + linearization + diagonal launch (gls_pencil_kernel<double, 5>,
 assemble_matrix_and_rhs); the budget is taken over the last complete step before the final one (the
 bench's instrumented step) in each file.
