@@ -5,7 +5,8 @@
 //   initial condition (nodal | L2projection | viscous, :784-827) -> time loop (integrate, first
 //   step with the BDF start-up, SDIRK stages; navier_stokes_base.cc:426-590) with the device
 //   Newton/GMRES (gls_newton_solve) -> post-processing (L2 error vs the analytical solution,
-//   enstrophy, kinetic energy, CFL; VTU/PVTU/PVD output).
+//   enstrophy, kinetic energy, CFL; forces and torques on the boundaries from the device-resident
+//   solution, `forces` section: log tables and <name>.<NN>.dat; VTU/PVTU/PVD output).
 // Results are printed as `key = value` lines and a final error table (own format); the numbers
 // are what the parity tests compare with the reference's outputs.
 //
@@ -20,6 +21,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -137,6 +139,7 @@ struct BC {
   std::string type;
   int id = 0, periodic_id = 1, periodic_direction = 0;
   Function f[3];
+  double cor[3] = {0, 0, 0};  // centre of rotation of the torque (subsection cor; function bcs only)
 };
 
 struct Params {
@@ -189,6 +192,10 @@ struct Params {
   int frac_type = 0;            // 0 fixed number, 1 fixed fraction (of the summed indicators)
   int64_t max_cells = 100000000;  // max number elements
   int max_level = 10;
+  // forces (parameters.cc:227-294): forces / torques on the boundaries after every solved iteration
+  bool calc_force = false, calc_torque = false, forces_verbose = false;
+  std::string force_name = "force", torque_name = "torque";
+  int forces_output_precision = 10, forces_display_precision = 6, forces_calc_frequency = 1, forces_output_frequency = 1;
 };
 
 Method parse_method(const std::string &s) {
@@ -284,6 +291,9 @@ Params read_params(const Prm &p, int dim) {
     if (b.type == "function") {
       const char *nm[3] = {"u", "v", "w"};
       for (int c = 0; c < dim; ++c) b.f[c] = Function(p, s + nm[c], dim, "0");
+      // the centre of rotation is read for function bcs only (boundary_conditions.h:197-218; z in 3D)
+      const char *cn[3] = {"x", "y", "z"};
+      for (int c = 0; c < dim; ++c) b.cor[c] = p.d(s + "cor/" + cn[c], 0.0);
     } else if (b.type != "noslip" && b.type != "periodic" && b.type != "slip") {
       die("bc %d: unknown type '%s'", i, b.type.c_str());
     }
@@ -358,6 +368,22 @@ Params read_params(const Prm &p, int dim) {
     if (P.amg_threshold < 0) die("linear solver/amg aggregation threshold must be >= 0");
     const std::string v = p.get("linear solver/verbosity", "verbose");
     if (v != "verbose" && v != "quiet") die("Unknown verbosity mode for the linear solver");
+  }
+  {  // forces (parameters.cc:227-294)
+    const std::string fs = "forces/";
+    const std::string v = p.get(fs + "verbosity", "quiet");
+    if (v != "verbose" && v != "quiet") die("Unknown verbosity mode for the forces");
+    P.forces_verbose = v == "verbose";
+    P.calc_force = p.b(fs + "calculate forces", false);
+    P.calc_torque = p.b(fs + "calculate torques", false);
+    P.force_name = p.get(fs + "force name", "force");
+    P.torque_name = p.get(fs + "torque name", "torque");
+    P.forces_output_precision = p.i(fs + "output precision", 10);
+    P.forces_display_precision = p.i(fs + "display precision", 6);
+    P.forces_calc_frequency = p.i(fs + "calculation frequency", 1);
+    P.forces_output_frequency = p.i(fs + "output frequency", 1);
+    if (P.forces_calc_frequency < 1 || P.forces_output_frequency < 1)
+      die("forces: calculation frequency and output frequency must be >= 1");
   }
   // restart (parameters.cc:759-798): checkpoint / restart files are out of scope; a prm
   // that asks for either fails here instead of silently running without it
@@ -1155,6 +1181,7 @@ struct Solver {
   }
 
   void release() {
+    release_boundary_plan();  // the plan belongs to the context destroyed below
     for (gls_ctx *g : mg_levels) gls_destroy(g);
     mg_levels.clear();
     for (gls_refined_mesh *R : mg_meshes) gls_octree_mesh_destroy(R);
@@ -1512,6 +1539,7 @@ struct Solver {
       attach_forest_mg();
     print_setup(std::pow(P.hi - P.lo, P.dim));
     std::printf("   Hanging node DoFs:            %lld\n", (long long)m.hang_dofs.size());
+    build_boundary_plan();
   }
 
   // Geometric multigrid on the forest's refinement hierarchy (gls_mg_attach_transfers): the levels are
@@ -1617,6 +1645,7 @@ struct Solver {
     }
     (void)N;
     print_setup(std::pow(P.hi - P.lo, P.dim));
+    build_boundary_plan();
   }
 
   // general meshes: the triangulation (gmsh file or GridGenerator grid with its manifolds and the
@@ -1900,6 +1929,7 @@ struct Solver {
     }
     alloc_vectors();
     print_setup(F.volume);
+    build_boundary_plan();
   }
   // setup_dofs' summary lines (gls_navier_stokes.cc:220-227)
   void print_setup(double volume) {
@@ -2420,6 +2450,18 @@ struct Solver {
       const double ke = volume_average(false);
       if (P.pp_verbose) std::printf("Kinetic energy : %s\n", g6(ke).c_str());
     }
+    // forces and torques: after every solved iteration, never at the initial postprocess
+    // (navier_stokes_base.cc:855-881), from the device-resident solution
+    if (!initial && loads_on()) {
+      if (P.calc_force) {
+        if (step % P.forces_calc_frequency == 0) loads_table(false);
+        if (step % P.forces_output_frequency == 0) loads_write(false);
+      }
+      if (P.calc_torque) {
+        if (step % P.forces_calc_frequency == 0) loads_table(true);
+        if (step % P.forces_output_frequency == 0) loads_write(true);
+      }
+    }
     if (!initial && P.analytical) {
       const auto e = l2_error();
       if (P.method == Method::steady) errors.push_back({(double)m.nc, e.first, e.second});
@@ -2714,6 +2756,216 @@ struct Solver {
     gls_fe_space_destroy(old_space);
     host_changed();
   }
+  // deal.II TableHandler::write_text cells (table_with_headers): numbers in fixed notation, every column
+  // as wide as its widest entry or its header, entries right-aligned, headers centred, one space after
+  // each column
+  static std::string fixed(double v, int d) {
+    char b[64];
+    std::snprintf(b, sizeof(b), "%.*f", d, v);
+    return std::string(b);
+  }
+  static std::string rpad(const std::string &t, size_t w) { return std::string(w > t.size() ? w - t.size() : 0, ' ') + t; }
+  static std::string lpad(const std::string &t, size_t w) { return t + std::string(w > t.size() ? w - t.size() : 0, ' '); }
+  static std::string centre(const std::string &t, size_t w) {
+    const size_t f = w > t.size() ? (w - t.size()) / 2 : 0, r = w > t.size() ? w - t.size() - f : 0;
+    return std::string(f, ' ') + t + std::string(r, ' ');
+  }
+  // a TableHandler of text columns: header[j] over col[j][row]
+  static std::string text_table(const std::vector<std::string> &header, const std::vector<std::vector<std::string>> &col) {
+    std::ostringstream o;
+    std::vector<size_t> w(header.size());
+    for (size_t j = 0; j < header.size(); ++j) {
+      w[j] = header[j].size();
+      for (const auto &t : col[j]) w[j] = std::max(w[j], t.size());
+      o << centre(header[j], w[j]) << ' ';
+    }
+    o << '\n';
+    for (size_t i = 0; !col.empty() && i < col[0].size(); ++i) {
+      for (size_t j = 0; j < header.size(); ++j) o << rpad(col[j][i], w[j]) << ' ';
+      o << '\n';
+    }
+    return o.str();
+  }
+
+  // ---- forces and torques on the boundaries (NavierStokesBase::postprocessing_forces / _torques,
+  // navier_stokes_base.cc:120-250; calculate_forces / calculate_torques, postprocessing_force.cc,
+  // postprocessing_torque.cc): the boundary faces of the current mesh with QGauss<dim-1>(k + 1) go to the
+  // device once per mesh (gls_boundary_plan_create; setup / setup_refined / setup_general run after every
+  // refinement), every evaluation is one pass over all boundaries from the device-resident solution
+  // (gls_boundary_loads) -- no download of the solution. Row i of the tables is boundary condition i: the
+  // faces whose boundary id equals bc i's id.
+  // --np: rank 0 evaluates on the gathered solution with a context of the whole mesh, as
+  // refine_kelly_general runs the Kelly estimate (per-rank partial integrals: DESIGN §7).
+  gls_boundary_plan *bplan = nullptr;
+  gls_ctx *bctx = nullptr;     // --np, rank 0: the whole-mesh context of the plan
+  double *d_bsol = nullptr;    // ... and the gathered solution on its device
+  std::vector<std::vector<std::array<double, 4>>> force_rows, torque_rows;  // per bc: (time, 3 components)
+  int loads_step = -1;         // the step whose loads are in load_f / load_t (one kernel pass serves both tables)
+  std::vector<double> load_f, load_t;
+  bool loads_on() const { return (P.calc_force || P.calc_torque) && !P.bcs.empty(); }
+  void release_boundary_plan() {
+    if (bplan) gls_boundary_plan_destroy(bplan);
+    bplan = nullptr;
+    if (bctx) gls_destroy(bctx);
+    bctx = nullptr;
+    if (d_bsol) (void)hipFree(d_bsol);
+    d_bsol = nullptr;
+  }
+  void build_boundary_plan() {
+    if (!loads_on()) return;
+    const int dim = P.dim, nq = P.k + 1, nqf = dim == 3 ? nq * nq : nq;  // QGauss<dim-1>(fe.degree + 1)
+    std::vector<int32_t> cell, bid;
+    std::vector<double> xi, jinv, normal, jxw, xq;
+    if (m.general) {
+      int64_t nf = 0;
+      ck(gls_fe_space_boundary_faces(space, nq, &nf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+         "gls_fe_space_boundary_faces");
+      std::vector<int32_t> face((size_t)nf);
+      cell.resize((size_t)nf);
+      bid.resize((size_t)nf);
+      xi.resize((size_t)(nf * nqf * dim));
+      jinv.resize((size_t)(nf * nqf * dim * dim));
+      normal.resize(xi.size());
+      jxw.resize((size_t)(nf * nqf));
+      xq.resize(xi.size());
+      if (nf)
+        ck(gls_fe_space_boundary_faces(space, nq, &nf, cell.data(), face.data(), bid.data(), xi.data(), jinv.data(),
+                                       normal.data(), jxw.data(), xq.data()),
+           "gls_fe_space_boundary_faces");
+    } else {
+      // hyper_cube lattice / forest: box cells (diagonal Jacobian from x0 and h); a face on the cube's
+      // face (d, side) carries the id the boundary conditions use there (face_bits: colorize 2 d + side,
+      // else 0); periodic directions have no boundary
+      std::vector<double> gx, gw;
+      gauss01(nq, gx, gw);
+      const double tol = 1e-12 * (m.hi - m.lo);
+      for (int64_t c = 0; c < m.nc; ++c)
+        for (int d = 0; d < dim; ++d)
+          for (int s = 0; s < 2; ++s) {
+            if ((m.pmask >> d) & 1) continue;
+            const double *x0 = &m.x0[(size_t)(c * dim)], *h = &m.h[(size_t)(c * dim)];
+            if (std::fabs(x0[d] + s * h[d] - (s ? m.hi : m.lo)) > tol) continue;
+            int t[2] = {0, 0}, nt = 0;
+            for (int e = 0; e < dim; ++e)
+              if (e != d) t[nt++] = e;
+            cell.push_back((int32_t)c);
+            bid.push_back(P.colorize ? 2 * d + s : 0);
+            for (int qb = 0; qb < (dim == 3 ? nq : 1); ++qb)
+              for (int qa = 0; qa < nq; ++qa) {
+                double X[3] = {0, 0, 0}, w = gw[(size_t)qa] * h[t[0]];
+                X[d] = s;
+                X[t[0]] = gx[(size_t)qa];
+                if (dim == 3) {
+                  X[t[1]] = gx[(size_t)qb];
+                  w *= gw[(size_t)qb] * h[t[1]];
+                }
+                for (int a = 0; a < dim; ++a) {
+                  xi.push_back(X[a]);
+                  normal.push_back(a == d ? (s ? 1.0 : -1.0) : 0.0);
+                  xq.push_back(x0[a] + X[a] * h[a]);
+                  for (int i = 0; i < dim; ++i) jinv.push_back(a == i ? 1.0 / h[a] : 0.0);
+                }
+                jxw.push_back(w);
+              }
+          }
+    }
+    // row of a face = the first bc with its id (faces of no bc are skipped)
+    const int nb = (int)P.bcs.size();
+    std::vector<int32_t> slot(cell.size(), -1);
+    for (size_t f = 0; f < cell.size(); ++f)
+      for (int i = nb - 1; i >= 0; --i)
+        if (P.bcs[(size_t)i].id == bid[f]) slot[f] = i;
+    if (world > 1 && rank != 0) return;
+    gls_ctx *g = ctx;
+    if (world > 1) {
+      g = bctx = make_context(m, C);
+      hk(hipMalloc(&d_bsol, sizeof(double) * (size_t)m.n_dofs()), "hipMalloc");
+    }
+    // degrees without a load kernel (2D Q3) end here with the library's message
+    ck(gls_boundary_plan_create(g, (int64_t)cell.size(), nqf, cell.data(), slot.data(), xi.data(), jinv.data(), normal.data(),
+                                jxw.data(), xq.data(), nb, &bplan),
+       "forces: gls_boundary_plan_create");
+  }
+  void boundary_loads() {  // load_f / load_t [bc][3] of the present solution, once per step
+    if (loads_step == step) return;
+    const int nb = (int)P.bcs.size();
+    load_f.assign((size_t)(3 * nb), 0.0);
+    load_t.assign((size_t)(3 * nb), 0.0);
+    // the reference takes the centre of rotation at bcFunctions[boundary id], not [i_bc]
+    // (postprocessing_torque.cc:69-72): bc i rotates about the cor of the bc NUMBER id_i (zero when that
+    // bc is no function bc; an id beyond the bcs reads past the reference's array: zero here)
+    std::vector<double> cor((size_t)(3 * nb), 0.0);
+    for (int i = 0; i < nb; ++i) {
+      const int id = P.bcs[(size_t)i].id;
+      if (id >= 0 && id < nb)
+        for (int a = 0; a < 3; ++a) cor[(size_t)(3 * i + a)] = P.bcs[(size_t)id].cor[a];
+    }
+    if (world > 1) {
+      need_host();  // collective: the owned values gathered on every rank
+      if (rank == 0) {
+        hk(hipMemcpy(d_bsol, present.data(), sizeof(double) * present.size(), hipMemcpyHostToDevice), "upload");
+        ck(gls_boundary_loads(bctx, bplan, d_bsol, P.nu, cor.data(), load_f.data(), load_t.data()), "gls_boundary_loads");
+      }
+    } else {
+      need_dev();
+      ck(gls_boundary_loads(ctx, bplan, d_present, P.nu, cor.data(), load_f.data(), load_t.data()), "gls_boundary_loads");
+    }
+    for (int i = 0; i < nb; ++i)  // bcs that repeat an id: the reference sums the same faces again
+      for (int j = 0; j < i; ++j)
+        if (P.bcs[(size_t)j].id == P.bcs[(size_t)i].id) {
+          for (int a = 0; a < 3; ++a) {
+            load_f[(size_t)(3 * i + a)] = load_f[(size_t)(3 * j + a)];
+            load_t[(size_t)(3 * i + a)] = load_t[(size_t)(3 * j + a)];
+          }
+          break;
+        }
+    loads_step = step;
+  }
+  // one of the two tables: the summary box + TableHandler on the log (verbosity = verbose, rank 0; every
+  // column at display precision, navier_stokes_base.cc:136-159, 204-226) and a row of each bc's .dat table
+  void loads_table(bool torque) {
+    SectionTimer::Scope ts(timer, torque ? "calculate_torques" : "calculate_forces");
+    boundary_loads();
+    if (rank != 0) return;
+    const std::vector<double> &v = torque ? load_t : load_f;
+    const int nb = (int)P.bcs.size(), ncol = torque ? 3 : P.dim;
+    if (P.forces_verbose) {
+      std::vector<std::string> header{"Boundary ID"};
+      std::vector<std::vector<std::string>> col((size_t)(1 + ncol));
+      const char *fn[3] = {"f_x", "f_y", "f_z"}, *tn[3] = {"T_x", "T_y", "T_z"};
+      for (int a = 0; a < ncol; ++a) header.push_back(torque ? tn[a] : fn[a]);
+      for (int i = 0; i < nb; ++i) {
+        col[0].push_back(std::to_string(P.bcs[(size_t)i].id));  // an integer column: the precision does not show
+        for (int a = 0; a < ncol; ++a) col[(size_t)(1 + a)].push_back(fixed(v[(size_t)(3 * i + a)], P.forces_display_precision));
+      }
+      std::printf("\n+------------------------------------------+\n|  %s summary                          |\n"
+                  "+------------------------------------------+\n%s",
+                  torque ? "Torque" : "Force ", text_table(header, col).c_str());
+    }
+    auto &rows = torque ? torque_rows : force_rows;
+    rows.resize((size_t)nb);
+    for (int i = 0; i < nb; ++i)
+      rows[(size_t)i].push_back({time, v[(size_t)(3 * i)], v[(size_t)(3 * i + 1)], v[(size_t)(3 * i + 2)]});
+  }
+  // write_output_forces / write_output_torques (navier_stokes_base.cc:1088-1121): <name>.<NN>.dat per bc,
+  // rewritten whole: time and the three components (f_z = 0 in 2D) at output precision
+  void loads_write(bool torque) {
+    SectionTimer::Scope ts(timer, torque ? "output_torques" : "output_forces");
+    if (rank != 0) return;
+    const auto &rows = torque ? torque_rows : force_rows;
+    const std::vector<std::string> header = torque ? std::vector<std::string>{"time", "T_x", "T_y", "T_z"}
+                                                   : std::vector<std::string>{"time", "f_x", "f_y", "f_z"};
+    for (size_t i = 0; i < P.bcs.size(); ++i) {
+      std::vector<std::vector<std::string>> col(4);
+      if (i < rows.size())
+        for (const auto &r : rows[i])
+          for (int a = 0; a < 4; ++a) col[(size_t)a].push_back(fixed(r[(size_t)a], P.forces_output_precision));
+      char nn[16];
+      std::snprintf(nn, sizeof(nn), ".%02d.dat", (int)i);
+      std::ofstream((torque ? P.torque_name : P.force_name) + nn) << text_table(header, col);
+    }
+  }
+
   // NavierStokesBase::finish_simulation's error table (navier_stokes_base.cc:382-424): deal.II
   // ConvergenceTable text layout — steady: cells | error_velocity + log2 reduction rate |
   // error_pressure + rate, errors in scientific notation with `precision` digits, rates fixed 2,
@@ -2726,17 +2978,6 @@ struct Solver {
       char b[64];
       std::snprintf(b, sizeof(b), "%.*e", precision, v);
       return std::string(b);
-    };
-    auto fixed = [](double v, int d) {
-      char b[64];
-      std::snprintf(b, sizeof(b), "%.*f", d, v);
-      return std::string(b);
-    };
-    auto rpad = [](const std::string &t, size_t w) { return std::string(w > t.size() ? w - t.size() : 0, ' ') + t; };
-    auto lpad = [](const std::string &t, size_t w) { return t + std::string(w > t.size() ? w - t.size() : 0, ' '); };
-    auto centre = [](const std::string &t, size_t w) {
-      const size_t f = w > t.size() ? (w - t.size()) / 2 : 0, r = w > t.size() ? w - t.size() - f : 0;
-      return std::string(f, ' ') + t + std::string(r, ' ');
     };
     const size_t n = errors.size();
     if (P.method == Method::steady) {

@@ -599,6 +599,26 @@ int gls_octree_mg_transfer(const gls_refined_mesh *fine, const gls_refined_mesh 
 int gls_kelly_estimate_mapped(gls_ctx *ctx, const double *sol, int variable, int64_t n_pieces, int nqf,
                               const int32_t *ca, const int32_t *cb, const double *xi, const double *g,
                               const double *jxw, const double *cell_diam, double *eta);
+/* Forces and torques on the boundaries: the reference's calculate_forces / calculate_torques
+ * (postprocessing_force.cc:67-110, postprocessing_torque.cc:67-125; called after every solved iteration,
+ * navier_stokes_base.cc:120-250, 855-881). Over the boundary faces, with QGauss<dim-1>(k + 1) and the
+ * cells' MappingQ: n = -(outward unit normal), sigma = nu (grad u + grad u^T) - p I,
+ *   f += sigma n JxW,   T += (x_q - cor) x (sigma n JxW)   (2D: T_z only; T always has 3 components).
+ * gls_boundary_plan_create uploads the face data of one mesh (host arrays: gls_fe_space_boundary_faces'
+ * layout -- per face its cell and its slot = row of the tables, slot -1 = skipped; per point xi / normal
+ * / xq [f][q][dim], jinv [f][q][dim][dim], jxw [f][q]; box meshes pass a diagonal jinv); rebuild it after
+ * an adaptation. gls_boundary_loads evaluates a solution vector on the DEVICE (the context's layout) in
+ * one pass over all boundaries (the reference makes one pass per boundary) and returns
+ * force[n_slots][3] / torque[n_slots][3] to HOST arrays; cor[n_slots][3] (host) is the centre of rotation
+ * of each slot. The sums use no atomics and a fixed order: two calls give bitwise identical tables.
+ * Kernels exist for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}; other degrees (2D Q3) are GLS_EINVAL. */
+typedef struct gls_boundary_plan gls_boundary_plan;
+int gls_boundary_plan_create(gls_ctx *ctx, int64_t n_faces, int nqf, const int32_t *cell, const int32_t *slot,
+                             const double *xi, const double *jinv, const double *normal, const double *jxw,
+                             const double *xq, int n_slots, gls_boundary_plan **plan);
+int gls_boundary_plan_destroy(gls_boundary_plan *plan);
+int gls_boundary_loads(gls_ctx *ctx, gls_boundary_plan *plan, const double *sol, double viscosity, const double *cor,
+                       double *force, double *torque);
 /* GridRefinement::refine_and_coarsen_fixed_number, refinement part (navier_stokes_base.cc:654-661;
  * serial deal.II rule): flags[i] = 1 for the int(top_fraction * n_cells) largest criteria (every
  * cell >= the threshold value). Returns the number of flagged cells. HOST arrays. */
@@ -739,6 +759,19 @@ int gls_fe_space_mg_transfer(const gls_fe_space *fine, const gls_fe_space *coars
  * cell_diam[n_cells] = cell->diameter(). Host arrays; call with ca == NULL for the count. */
 int gls_fe_space_kelly_faces(const gls_fe_space *space, int nq, int64_t *n_pieces, int32_t *ca, int32_t *cb,
                              double *xi, double *g, double *jxw, double *cell_diam);
+/* Boundary faces of the active cells, for the reference's force / torque post-processing
+ * (postprocessing_force.cc, postprocessing_torque.cc): per face its cell, local face 2*d + side and
+ * boundary id; per point q of QGauss<dim-1>(nq) (nqf = nq^(dim-1), first tangential direction fastest)
+ * the reference coordinates xi[f][q][dim], the inverse Jacobian jinv[f][q][a][i] = d xi_a / d x_i
+ * (grad u = J^-T grad_xi u), the OUTWARD unit normal[f][q][dim], jxw[f][q] and the mapped point
+ * xq[f][q][dim], with the MappingQ geometry of the Kelly pieces (the cell's cell_mapping degree). Every
+ * face with at_boundary() is listed, on adapted meshes once per active cell. The faces of a periodic
+ * pair are NOT taken out: they are boundary faces of the triangulation and the reference would integrate
+ * over them for a bc of type periodic with that id, so they are listed with their id. Host arrays;
+ * call with all arrays NULL for the count. */
+int gls_fe_space_boundary_faces(const gls_fe_space *space, int nq, int64_t *n_faces, int32_t *cell, int32_t *face,
+                                int32_t *boundary_id, double *xi, double *jinv, double *normal, double *jxw,
+                                double *xq);
 
 /* ------------------------------------------------------------------------------------------
  * Drop-in I/O surface, host side.

@@ -3521,6 +3521,93 @@ int gls_kelly_estimate_mapped(gls_ctx *c, const double *sol, int variable, int64
   return GLS_OK;
 }
 
+// --------------------------------------------------------------------------------------------
+// Forces and torques on the boundaries (postprocessing_force.cc, postprocessing_torque.cc): the face
+// data of one mesh uploaded once (plan), every evaluation one pass over all boundaries on the device
+// --------------------------------------------------------------------------------------------
+struct gls_boundary_plan {
+  gls_ctx *ctx = nullptr;
+  int64_t n_faces = 0, n_pts = 0;
+  int nqf = 0, n_slots = 0;
+  DevBuf<int32_t> cell, slot;
+  DevBuf<double> xi, jinv, normal, jxw, xq, cor, partial, out;
+};
+
+namespace {
+int boundary_degrees(gls_ctx *c, const char *who) {
+  if (!gls::boundary_loads_supported(c->dim, c->k, c->kp))
+    return set_err(GLS_EINVAL,
+                   "%s: FE_Q(%d)-FE_Q(%d) in %dD has no load kernel (velocity / pressure orders (1,1), (2,1), (2,2); "
+                   "2D Q3 is not supported)",
+                   who, c->k, c->kp, c->dim);
+  return GLS_OK;
+}
+}  // namespace
+
+int gls_boundary_plan_create(gls_ctx *c, int64_t n_faces, int nqf, const int32_t *cell, const int32_t *slot,
+                             const double *xi, const double *jinv, const double *normal, const double *jxw,
+                             const double *xq, int n_slots, gls_boundary_plan **out) {
+  GLS_TRY(check_ctx(c));
+  if (!out || n_faces < 0 || nqf < 1 || n_slots < 1 || n_slots > 4096 ||
+      (n_faces > 0 && (!cell || !slot || !xi || !jinv || !normal || !jxw || !xq)))
+    return set_err(GLS_EINVAL, "gls_boundary_plan_create: bad arguments");
+  GLS_TRY(boundary_degrees(c, "gls_boundary_plan_create"));
+  for (int64_t f = 0; f < n_faces; ++f)
+    if (cell[f] < 0 || cell[f] >= c->n_cells || slot[f] < -1 || slot[f] >= n_slots)
+      return set_err(GLS_EINVAL, "gls_boundary_plan_create: face %lld: cell %d / slot %d out of range", (long long)f,
+                     cell[f], slot[f]);
+  std::unique_ptr<gls_boundary_plan> p(new gls_boundary_plan);
+  p->ctx = c;
+  p->n_faces = n_faces;
+  p->nqf = nqf;
+  p->n_slots = n_slots;
+  p->n_pts = n_faces * nqf;
+  const size_t np = (size_t)p->n_pts, dim = (size_t)c->dim;
+  GLS_TRY(p->cell.upload(cell, (size_t)n_faces));
+  GLS_TRY(p->slot.upload(slot, (size_t)n_faces));
+  GLS_TRY(p->xi.upload(xi, np * dim));
+  GLS_TRY(p->jinv.upload(jinv, np * dim * dim));
+  GLS_TRY(p->normal.upload(normal, np * dim));
+  GLS_TRY(p->jxw.upload(jxw, np));
+  GLS_TRY(p->xq.upload(xq, np * dim));
+  GLS_TRY(p->cor.alloc((size_t)n_slots * 3));
+  GLS_TRY(p->partial.alloc((size_t)std::max<int64_t>(gls::boundary_loads_blocks(p->n_pts), 1) * n_slots * 6));
+  GLS_TRY(p->out.alloc((size_t)n_slots * 6));
+  *out = p.release();
+  return GLS_OK;
+}
+
+int gls_boundary_plan_destroy(gls_boundary_plan *plan) {
+  delete plan;
+  return GLS_OK;
+}
+
+int gls_boundary_loads(gls_ctx *c, gls_boundary_plan *p, const double *sol, double viscosity, const double *cor,
+                       double *force, double *torque) {
+  GLS_TRY(check_ctx(c));
+  if (!p || p->ctx != c) return set_err(GLS_EINVAL, "gls_boundary_loads: the plan belongs to another context");
+  if (!sol || !cor || !force || !torque) return set_err(GLS_EINVAL, "gls_boundary_loads: bad arguments");
+  GLS_TRY(boundary_degrees(c, "gls_boundary_loads"));
+  const int ns = p->n_slots;
+  std::fill(force, force + 3 * ns, 0.0);
+  std::fill(torque, torque + 3 * ns, 0.0);
+  if (p->n_pts == 0) return GLS_OK;
+  HIP_TRY(hipMemcpyAsync(p->cor.p, cor, sizeof(double) * 3 * (size_t)ns, hipMemcpyHostToDevice, c->stream));
+  const int32_t *pn = c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;  // equal order: shared nodes
+  HIP_TRY(gls::launch_boundary_loads(c->dim, c->k, c->kp, c->cell_vnodes.p, pn, sol, (int64_t)c->dim * c->n_vnodes,
+                                     p->n_pts, p->nqf, p->cell.p, p->slot.p, p->xi.p, p->jinv.p, p->normal.p, p->jxw.p,
+                                     p->xq.p, viscosity, p->cor.p, ns, p->partial.p, p->out.p, c->stream));
+  std::vector<double> o((size_t)ns * 6);
+  HIP_TRY(hipMemcpyAsync(o.data(), p->out.p, sizeof(double) * o.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int s = 0; s < ns; ++s)
+    for (int i = 0; i < 3; ++i) {
+      force[3 * s + i] = o[(size_t)(6 * s + i)];
+      torque[3 * s + i] = o[(size_t)(6 * s + 3 + i)];
+    }
+  return GLS_OK;
+}
+
 int gls_set_lattice(gls_ctx *c, int n1d, const int64_t *l2g) {
   GLS_TRY(check_ctx(c));
   if (c->dim != 3 || n1d < 2 || !l2g) return set_err(GLS_EINVAL, "gls_set_lattice: 3D, n1d >= 2, map required");

@@ -184,6 +184,20 @@ hipError_t launch_kelly(int dim, int m, const int32_t *cell_nodes, const int32_t
                         const double *sol, int n_cells, int ncomp, int64_t base, int stride, const KellyTables &T,
                         double *eta, hipStream_t s);
 
+// ---- boundary forces and torques (gls_boundary.hip): every boundary in one pass. Per face point
+// pt = face * nqf + q: xi / normal / xq [pt][dim], jinv [pt][dim][dim] (d xi_a / d x_i), jxw [pt];
+// per face its cell and its slot (row of the tables, -1: skipped); cor [n_slots][3]. The velocity of
+// node n is at sol[n * dim + c], the pressure of node n at sol[pbase + n]. partial:
+// boundary_loads_blocks(n_pts) * n_slots * 6 doubles; out [n_slots][6] = f_x f_y f_z T_x T_y T_z, summed in a
+// fixed order (bitwise reproducible). Instantiated for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}.
+int64_t boundary_loads_blocks(int64_t n_pts);
+bool boundary_loads_supported(int dim, int k, int kp);
+hipError_t launch_boundary_loads(int dim, int k, int kp, const int32_t *cell_vnodes, const int32_t *cell_pnodes,
+                                 const double *sol, int64_t pbase, int64_t n_pts, int nqf, const int32_t *fcell,
+                                 const int32_t *fslot, const double *xi, const double *jinv, const double *normal,
+                                 const double *jxw, const double *xq, double nu, const double *cor, int n_slots,
+                                 double *partial, double *out, hipStream_t s);
+
 // ---- geometric multigrid (gls_mg_kernels.hip): nested Qk node lattices (boxes), k <= 2
 hipError_t mg_inject(const double *fine, double *coarse, const int nf[3], const int nc[3], hipStream_t s);
 // one-pass 3D transfer with per-axis tap tables [n_out][5] (index, weight) and tap counts [n_out]

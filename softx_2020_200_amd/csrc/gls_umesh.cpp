@@ -2645,6 +2645,92 @@ int gls_fe_space_kelly_faces(const gls_fe_space *sp, int nq, int64_t *n_pieces, 
   return GLS_OK;
 }
 
+// Boundary faces of the active cells for the force / torque integrals (postprocessing_force.cc:67-110,
+// postprocessing_torque.cc:67-125: every face with at_boundary(), whatever its id -- the faces of a
+// periodic pair included, the reference integrates over them for a bc of that id). QGauss<dim-1>(nq)
+// on each face with the cell's MappingQ (the jacobian() of the Kelly pieces, so the mapping degree the
+// space records in cell_mapping): per point the reference coordinates, jinv[a][i] = d xi_a / d x_i
+// (grad u = J^-T grad_xi u), the outward unit normal J^-T e_d / |J^-T e_d| (sign by the face's
+// side), JxW = |t_u x t_v| w with t = J e_t (2D: |t_u| w) and the mapped point. On adapted meshes
+// every active cell's boundary face is listed once (a boundary face has no hanging partner). Null
+// arrays: count only.
+int gls_fe_space_boundary_faces(const gls_fe_space *sp, int nq, int64_t *n_faces, int32_t *cell, int32_t *face,
+                                int32_t *bid, double *xi, double *jinv, double *normal, double *jxw, double *xq) {
+  if (!sp || !sp->impl_ || !n_faces || nq < 1 || nq > 8)
+    return gls_io_set_error(GLS_EINVAL, "gls_fe_space_boundary_faces: arguments");
+  const bool fill = cell || face || bid || xi || jinv || normal || jxw || xq;
+  if (fill && !(cell && face && bid && xi && jinv && normal && jxw && xq))
+    return gls_io_set_error(GLS_EINVAL, "gls_fe_space_boundary_faces: all arrays or none");
+  const FESpaceImpl &F = *static_cast<const FESpaceImpl *>(sp->impl_);
+  const int dim = sp->dim, k = sp->k, k1 = k + 1, nl = dim == 2 ? k1 * k1 : k1 * k1 * k1;
+  const int nqf = dim == 3 ? nq * nq : nq;
+  double gx[8], gw[8];
+  gauss01(nq, gx, gw);
+  int64_t cnt = 0;
+  for (int64_t c = 0; c < sp->n_cells; ++c)
+    for (int f = 0; f < 2 * dim; ++f) {
+      const int id = F.face_bid[(size_t)(c * 2 * dim + f)];
+      if (id < 0) continue;
+      if (!fill) {
+        ++cnt;
+        continue;
+      }
+      const int d = f / 2, s = f & 1;
+      int t[2] = {0, 0}, nt = 0;
+      for (int e = 0; e < dim; ++e)
+        if (e != d) t[nt++] = e;
+      cell[cnt] = (int32_t)c;
+      face[cnt] = f;
+      bid[cnt] = id;
+      for (int qb = 0; qb < (dim == 3 ? nq : 1); ++qb)
+        for (int qa = 0; qa < nq; ++qa) {
+          const int64_t pt = cnt * nqf + qa + nq * qb;
+          double X[3] = {0, 0, 0}, J[3][3], JT[3][3];
+          X[d] = s;
+          X[t[0]] = gx[qa];
+          if (dim == 3) X[t[1]] = gx[qb];
+          jacobian(*sp, c, X, J);
+          for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) JT[i][j] = J[j][i];
+          for (int i = 0; i < dim; ++i) {  // column i of J^-1
+            double e[3] = {0, 0, 0}, y[3];
+            e[i] = 1.0;
+            solve3(J, e, y, dim);
+            for (int a = 0; a < dim; ++a) jinv[(pt * dim + a) * dim + i] = y[a];
+          }
+          double e[3] = {0, 0, 0}, n[3] = {0, 0, 0}, l = 0;
+          e[d] = s ? 1.0 : -1.0;
+          solve3(JT, e, n, dim);
+          for (int i = 0; i < dim; ++i) l += n[i] * n[i];
+          l = std::sqrt(l);
+          V3 tu{0, 0, 0}, tv{0, 0, 0};
+          for (int i = 0; i < dim; ++i) {
+            tu[i] = J[i][t[0]];
+            if (dim == 3) tv[i] = J[i][t[1]];
+          }
+          const double area = dim == 2 ? nrm(tu) : nrm(cross(tu, tv));
+          jxw[pt] = area * gw[qa] * (dim == 3 ? gw[qb] : 1.0);
+          double v[3][4], dv[3][4], x[3] = {0, 0, 0};
+          for (int a = 0; a < dim; ++a)
+            for (int b = 0; b <= k; ++b) lagd1(k, b, X[a], v[a][b], dv[a][b]);
+          for (int b = 0; b < nl; ++b) {
+            const int ib[3] = {b % k1, (b / k1) % k1, b / (k1 * k1)};
+            double w = 1.0;
+            for (int a = 0; a < dim; ++a) w *= v[a][ib[a]];
+            for (int i = 0; i < dim; ++i) x[i] += w * sp->cell_support[((size_t)c * nl + b) * dim + i];
+          }
+          for (int i = 0; i < dim; ++i) {
+            xi[pt * dim + i] = X[i];
+            normal[pt * dim + i] = n[i] / l;
+            xq[pt * dim + i] = x[i];
+          }
+        }
+      ++cnt;
+    }
+  *n_faces = cnt;
+  return GLS_OK;
+}
+
 // Node normals of the boundary faces with id `boundary_id` (VectorTools::
 // compute_no_normal_flux_constraints, gls_navier_stokes.cc:100-110): at every velocity node on such a
 // face, the normalised sum of the adjacent faces' outward unit normals (J^-T e_d of the cell's

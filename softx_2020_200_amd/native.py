@@ -45,6 +45,7 @@ EXPORTS = [
     "gls_kelly_estimate_mapped", "gls_fe_space_boundary_normals", "gls_fe_space_boundary_normal_sets",
     "gls_octree_coarsen_to", "gls_octree_mg_transfer", "gls_mg_attach_transfers", "gls_umesh_coarsen_to",
     "gls_fe_space_mg_transfer", "gls_forest_bricks",
+    "gls_fe_space_boundary_faces", "gls_boundary_plan_create", "gls_boundary_plan_destroy", "gls_boundary_loads",
 ]
 
 
@@ -213,6 +214,10 @@ def load():
     L.gls_fe_space_boundary_normals.argtypes = [C.POINTER(FESpace), C.c_int, d]
     L.gls_fe_space_boundary_normal_sets.argtypes = [C.POINTER(FESpace), C.c_int, C.POINTER(C.c_int32), d]
     L.gls_kelly_estimate_mapped.argtypes = [vp, vp, C.c_int, i64, C.c_int, pi32, pi32, d, d, d, d, vp]
+    L.gls_fe_space_boundary_faces.argtypes = [C.POINTER(FESpace), C.c_int, C.POINTER(i64), pi32, pi32, pi32, d, d, d, d, d]
+    L.gls_boundary_plan_create.argtypes = [vp, i64, C.c_int, pi32, pi32, d, d, d, d, d, C.c_int, C.POINTER(vp)]
+    L.gls_boundary_plan_destroy.argtypes = [vp]
+    L.gls_boundary_loads.argtypes = [vp, vp, vp, C.c_double, d, d, d]
     _lib = L
     return L
 
@@ -863,6 +868,32 @@ class GLSContext:
                                                _dp(f["diam"]), _ptr(out)), "gls_kelly_estimate_mapped")
         return out
 
+    def boundary_loads(self, faces, slots, n_slots, sol, viscosity, cor):
+        """Forces and torques on the boundaries (gls_boundary_plan_create + gls_boundary_loads): faces from
+        FESpaceHandle.boundary_faces(k + 1) (or a dict with the same keys), slots[f] = the row of face f in
+        the tables (-1: skipped), cor[n_slots][3] the centres of rotation, sol a device vector. Returns
+        (force[n_slots][3], torque[n_slots][3]) as numpy arrays. The plan (the uploaded face data) lives for
+        this call; a time loop keeps one per mesh through the C interface, as the application does."""
+        f = {k: np.ascontiguousarray(v) for k, v in faces.items() if isinstance(v, np.ndarray)}
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        if sl.shape != (len(f["cell"]),):
+            raise GLSError("boundary_loads: one slot per face")
+        cor = np.ascontiguousarray(cor, dtype=np.float64)
+        if cor.shape != (int(n_slots), 3):
+            raise GLSError("boundary_loads: cor is [n_slots][3]")
+        p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        plan = C.c_void_p()
+        check(self.L.gls_boundary_plan_create(self.h, len(sl), int(faces["nqf"]), p32(f["cell"]), p32(sl), _dp(f["xi"]),
+                                              _dp(f["jinv"]), _dp(f["normal"]), _dp(f["jxw"]), _dp(f["xq"]),
+                                              int(n_slots), C.byref(plan)), "gls_boundary_plan_create")
+        force, torque = np.zeros((int(n_slots), 3)), np.zeros((int(n_slots), 3))
+        try:
+            check(self.L.gls_boundary_loads(self.h, plan, _ptr(sol), float(viscosity), _dp(cor), _dp(force), _dp(torque)),
+                  "gls_boundary_loads")
+        finally:
+            self.L.gls_boundary_plan_destroy(plan)
+        return force, torque
+
     def mg_transfer(self, level, direction, v, out):
         """Restrict (direction 0: level -> level+1) or prolongate (1: level+1 -> level) a device vector."""
         check(self.L.gls_mg_transfer(self.h, int(level), int(direction), _ptr(v), _ptr(out)), "gls_mg_transfer")
@@ -1032,7 +1063,8 @@ class UMesh:
 
 class FESpaceHandle:
     """A live gls_fe_space: .data (numpy dict), transfer_from (SolutionTransfer from an earlier space
-    of the same mesh), kelly_faces (face pieces with MappingQ geometry)."""
+    of the same mesh), kelly_faces (face pieces with MappingQ geometry), boundary_faces (the boundary
+    faces of the force / torque integrals)."""
 
     def __init__(self, L, ptr):
         self.L, self.ptr = L, ptr
@@ -1097,6 +1129,27 @@ class FESpaceHandle:
         check(self.L.gls_fe_space_kelly_faces(self.ptr, int(nq), C.byref(n), p32(ca), p32(cb), _dp(xi), _dp(g),
                                               _dp(jxw), _dp(diam)), "gls_fe_space_kelly_faces")
         return dict(ca=ca, cb=cb, xi=xi, g=g, jxw=jxw, diam=diam, nqf=nqf)
+
+    def boundary_faces(self, nq):
+        """Boundary faces of the active cells with their QGauss<dim-1>(nq) geometry
+        (gls_fe_space_boundary_faces): cell, face (2*d + side), id per face; xi, normal (outward), xq
+        [n][nqf][dim], jinv [n][nqf][dim][dim] (d xi_a / d x_i), jxw [n][nqf]."""
+        n = C.c_int64()
+        z32 = C.POINTER(C.c_int32)()
+        zd = C.POINTER(C.c_double)()
+        check(self.L.gls_fe_space_boundary_faces(self.ptr, int(nq), C.byref(n), z32, z32, z32, zd, zd, zd, zd, zd),
+              "gls_fe_space_boundary_faces")
+        dim, nf = self.data["dim"], int(n.value)
+        nqf = nq ** (dim - 1)
+        cell, face, bid = np.zeros(nf, np.int32), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
+        xi, normal, xq = np.zeros((nf, nqf, dim)), np.zeros((nf, nqf, dim)), np.zeros((nf, nqf, dim))
+        jinv, jxw = np.zeros((nf, nqf, dim, dim)), np.zeros((nf, nqf))
+        p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        if nf:
+            check(self.L.gls_fe_space_boundary_faces(self.ptr, int(nq), C.byref(n), p32(cell), p32(face), p32(bid), _dp(xi),
+                                                     _dp(jinv), _dp(normal), _dp(jxw), _dp(xq)),
+                  "gls_fe_space_boundary_faces")
+        return dict(cell=cell, face=face, id=bid, xi=xi, jinv=jinv, normal=normal, jxw=jxw, xq=xq, nqf=nqf)
 
 
 def _fe_space_dict(m):
