@@ -280,6 +280,14 @@ int gls_mg_smoother_apply(gls_ctx *ctx, const double *v, double *y);
  * prolongates a level-`level`+1 vector onto level `level` (exact Qk interpolation). Constrained
  * rows are not touched here; the V-cycle zeroes them. */
 int gls_mg_transfer(gls_ctx *ctx, int level, int direction, const double *in, double *out);
+/* Debug / test entry: the coarse right-hand side the V-cycle forms on level `level`+1 from level `level`'s
+ * iterate x and right-hand side b at the current state, bc = R (b - A_s x) with the constrained coarse
+ * rows zeroed (DEVICE pointers; x, b: level `level` vectors, bc: level `level`+1). Where the level is
+ * eligible (one rank, FP32 smoothing on the hyper_cube's Q2 bricks, nested lattice levels) the residual
+ * is restricted inside the smoother's J.v launch and summed on the coarse lattice; else, or with
+ * GLS_MG_FUSE_TRANSFER=0 / GLS_MG_NO_FUSE in the environment, by the separate residual, transfer and
+ * zeroing launches. *fused (may be NULL) reports which of the two ran. */
+int gls_mg_residual_restrict(gls_ctx *ctx, int level, const double *x, const double *b, double *bc, int *fused);
 /* Lattice embedding of a (rank-local) mesh: its velocity nodes are a subset of the global n1d^3
  * Qk node lattice of hyper_cube in canonical numbering (global id = x + n1d*(y + n1d*z)), local
  * node i being global node local_to_global[i] (host array, n_vnodes entries). The local nodes

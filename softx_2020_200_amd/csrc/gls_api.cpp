@@ -488,6 +488,9 @@ struct gls_ctx {
       DevBuf<int32_t> pi[3], ri[3], pc[3], rc[3];
       DevBuf<double> pw[3], rw[3];
       bool two_pass = false;  // the xy tiles of mg_transfer_2pass fit these tables
+      // Q2: every axis' taps are the brick-local 5 <-> 3 table the pencil J.v's in-kernel restriction uses
+      // (fine nodes 4 c .. 4 c + 4 from coarse nodes 2 c .. 2 c + 2: 1 | 3/8 3/4 -1/8 | 1 | -1/8 3/4 3/8 | 1)
+      bool q2_brick = false;
     };
     std::vector<std::unique_ptr<Taps>> taps;
     // general hierarchies (gls_mg_attach_transfers): per level pair the prolongation P (fine rows), the
@@ -2814,6 +2817,54 @@ int mg_prolong(gls_ctx *c, int l, double *xc, double *y, bool add = false) {
   return GLS_OK;
 }
 
+// The residual and its restriction in one J.v launch (single rank, FP32 smoothing on the cube's Q2 bricks,
+// nested lattice levels with the two-pass taps): the pencil J.v restricts each brick's part of b - A x to the
+// brick's coarse cell, and one sum over the coarse lattice forms the coarse right-hand side with its constrained
+// rows zeroed. The fine residual vector, the slab, its sum and both restriction passes are not needed.
+// GLS_MG_FUSE_TRANSFER=0 (read per call) or GLS_MG_NO_FUSE keep the separate launches.
+bool mg_fused_restrict_ok(gls_ctx *c, int l) {
+  auto &mg = c->mg;
+  if (l < 0 || l + 1 >= (int)mg.lev.size() || mg.csr || mg.boxed || (size_t)l >= mg.taps.size()) return false;
+  const char *e = std::getenv("GLS_MG_FUSE_TRANSFER");
+  if ((e && std::atoi(e) == 0) || std::getenv("GLS_MG_NO_FUSE") != nullptr) return false;
+  gls_ctx *g = mg.lev[(size_t)l], *h = mg.lev[(size_t)l + 1];
+  const auto &T = *mg.taps[(size_t)l];
+  const int64_t nc1 = 2 * (int64_t)g->cube_nb1 + 1;
+  return T.two_pass && T.q2_brick && g->smooth_f32 && g->use_brick && g->use_qdata && !g->use_colors && !g->dist.on &&
+         !g->hang.on && !g->oct.on && g->k == 2 && g->cube_nb1 > 0 && g->cube_nb1 < 1024 && g->use_slab && !g->srf &&
+         gls::pencil_enabled() && gls::brick_fused_jacobi_supported(g->k) && !h->dist.on && !h->hang.on &&
+         h->n_vnodes == nc1 * nc1 * nc1 && g->stream == c->stream;
+}
+// bc (level l + 1) = R (b - A x) with the constrained coarse rows zeroed (x, b on level l). first_omega > 0
+// (first_sweep_fusable levels): x is not read but formed and stored as the first damped-Jacobi sweep from 0,
+// as in jacobian_apply_f32
+int mg_residual_restrict_fused(gls_ctx *c, int l, double *x, const double *b, double *bc, double first_omega = 0.0) {
+  gls_ctx *g = c->mg.lev[(size_t)l], *h = c->mg.lev[(size_t)l + 1];
+  if (!g->u) return set_err(GLS_EINVAL, "gls_set_state was not called");
+  GLS_TRY(ensure_diag(g));
+  GLS_TRY(ensure_qdata32(g, !g->smooth_oseen));
+  gls::OpParams P = make_params(g, true);
+  P.qdf = g->qdata32.p;
+  P.oseen = g->smooth_oseen ? 1 : 0;
+  P.v = x;
+  P.rb = b;
+  P.cube_nb1 = g->cube_nb1;
+  if (first_omega > 0.0) {
+    P.jx0 = x;
+    P.jd = g->diag.p;
+    P.jomega = first_omega;
+  }
+  P.slab = brick_slab(g);  // holds the bricks' coarse element vectors [brick][27][4] here (the slab is larger)
+  if (!P.slab) return set_err(GLS_EHIP, "brick slab allocation failed");
+  {
+    TimedLaunch t(g, 4);
+    HIP_TRY(gls::launch_pencil_jv_restrict(P, g->tables, c->stream));
+  }
+  TimedLaunch t(g, 5);
+  HIP_TRY(gls::brick_restrict_sum_cube(g->cube_nb1, P.slab, h->n_vnodes, bc, h->vmask.p, c->stream));
+  return GLS_OK;
+}
+
 // coarsest level by HIP graph (opt-in, GLS_MG_GRAPH=1: measured at 128^3, 138.0 vs 138.6 ms per
 // Newton step -- the coarse sweeps are bound by the kernels' own latency, not by launch overhead,
 // profiles/r01_coarse_graph_bench.txt): one rank, fused brick sweeps, the level's own b / x buffers (the
@@ -3075,17 +3126,22 @@ int mg_vcycle(gls_ctx *c, int l, const double *b, double *x) {
   }
   if (l == L - 1) return GLS_OK;
   // residual -> coarse right-hand side: restrict the owned rows, export-add coarse ghost rows
-  if (first_fused) {
-    GLS_TRY(jacobian_apply_f32(g, x, y, b, om, g->smooth_oseen));  // x = omega D^-1 b, y = b - A x
-  } else if (pre > 0) {
-    GLS_TRY(smoother_apply(g, x, y, b));  // y = b - A x
-  } else {
-    HIP_TRY(gls::vec_copy(y, b, n, s));  // x = 0: the residual is b
-  }
   gls_ctx *h = mg.lev[l + 1];
   double *bc = mgbuf(c, l + 1, MB_B), *xc = mgbuf(c, l + 1, MB_X);
-  GLS_TRY(mg_restrict(c, l, y, bc));
-  HIP_TRY(gls::vec_set_indexed(bc, h->con_dofs.p, nullptr, (int64_t)h->con_dofs.n, s));
+  if (pre > 0 && mg_fused_restrict_ok(c, l)) {
+    // bc = R (b - A x), constrained rows zeroed: one J.v + one sum (first_fused: x = omega D^-1 b formed there too)
+    GLS_TRY(mg_residual_restrict_fused(c, l, x, b, bc, first_fused ? om : 0.0));
+  } else {
+    if (first_fused) {
+      GLS_TRY(jacobian_apply_f32(g, x, y, b, om, g->smooth_oseen));  // x = omega D^-1 b, y = b - A x
+    } else if (pre > 0) {
+      GLS_TRY(smoother_apply(g, x, y, b));  // y = b - A x
+    } else {
+      HIP_TRY(gls::vec_copy(y, b, n, s));  // x = 0: the residual is b
+    }
+    GLS_TRY(mg_restrict(c, l, y, bc));
+    HIP_TRY(gls::vec_set_indexed(bc, h->con_dofs.p, nullptr, (int64_t)h->con_dofs.n, s));
+  }
   GLS_TRY(mg_vcycle(c, l + 1, bc, xc));
   // prolongate the coarse correction (ghost values imported first). x += P xc in the transfer's
   // store on one rank: the coarse correction vanishes on the coarse Dirichlet rows (zero rhs rows,
@@ -3348,6 +3404,24 @@ int gls_mg_transfer(gls_ctx *c, int level, int direction, const double *in, doub
   double *xc = mgbuf(c, level + 1, MB_X);  // ghost import writes into the coarse vector: work on a copy
   HIP_TRY(gls::vec_copy(xc, in, mg.lev[(size_t)level + 1]->n_dofs, c->stream));
   return mg_prolong(c, level, xc, out);
+}
+
+int gls_mg_residual_restrict(gls_ctx *c, int level, const double *x, const double *b, double *bc, int *fused) {
+  GLS_TRY(check_ctx(c));
+  auto &mg = c->mg;
+  if (!mg.on) return set_err(GLS_EINVAL, "gls_mg_residual_restrict: no multigrid attached");
+  if (level < 0 || level + 1 >= (int)mg.lev.size() || !x || !b || !bc)
+    return set_err(GLS_EINVAL, "gls_mg_residual_restrict: bad level / pointers");
+  GLS_TRY(mg_prepare(c));  // the levels' states, as the V-cycle sees them
+  const bool f = mg_fused_restrict_ok(c, level);
+  if (fused) *fused = f ? 1 : 0;
+  if (f) return mg_residual_restrict_fused(c, level, const_cast<double *>(x), b, bc);
+  gls_ctx *g = mg.lev[(size_t)level], *h = mg.lev[(size_t)level + 1];
+  double *y = mgbuf(c, level, MB_Y);
+  GLS_TRY(smoother_apply(g, x, y, b));
+  GLS_TRY(mg_restrict(c, level, y, bc));
+  HIP_TRY(gls::vec_set_indexed(bc, h->con_dofs.p, nullptr, (int64_t)h->con_dofs.n, c->stream));
+  return GLS_OK;
 }
 
 // --------------------------------------------------------------------------------------------
@@ -3755,7 +3829,8 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
   for (int l = 0; l + 1 < p->n_levels; ++l) {
     std::unique_ptr<gls_ctx::MG::Taps> T(new gls_ctx::MG::Taps);
     T->two_pass = true;
-    xwork = std::max(xwork, (size_t)4 * mg.dims[l + 1][0] * mg.dims[l + 1][1] * mg.dims[l][2]);
+    T->q2_brick = K == 2;
+    xwork =std::max(xwork, (size_t)4 * mg.dims[l + 1][0] * mg.dims[l + 1][1] * mg.dims[l][2]);
     for (int a = 0; a < 3; ++a) {
       const int nf = mg.dims[l][a], nc = mg.dims[l + 1][a], ncc = (nf - 1) / (2 * K);
       std::vector<int32_t> pi((size_t)nf * 5, 0), ri((size_t)nc * 5, 0);
@@ -3781,6 +3856,18 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
           ++rn[(size_t)j];
         }
         pn[(size_t)i] = np;
+        if (K == 2) {  // the closed form of the in-kernel restriction, checked tap by tap
+          static const double W[5][3] = {{1, 0, 0}, {0.375, 0.75, -0.125}, {0, 1, 0}, {-0.125, 0.75, 0.375}, {0, 0, 1}};
+          const int m = i - 4 * cc;
+          int nz = 0;
+          for (int q = 0; q < 3; ++q) nz += W[m][q] != 0.0;
+          bool same = np == nz;
+          for (int e = 0; same && e < np; ++e) {
+            const int q = pi[(size_t)i * 5 + e] - 2 * cc;
+            same = q >= 0 && q < 3 && pw[(size_t)i * 5 + e] == W[m][q];
+          }
+          T->q2_brick = T->q2_brick && same && nf == 2 * nc - 1;
+        }
       }
       if (a < 2)
         T->two_pass = T->two_pass && gls::mg_transfer_tile_fits(0, a, nf, pi.data(), pn.data()) &&

@@ -1371,6 +1371,97 @@ hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *
   return hipGetLastError();
 }
 
+// The V-cycle's restricted residual on the coarse hyper_cube lattice (Q2): a fine brick is one coarse
+// cell, and the pencil J.v (RST) left each brick's residual restricted to that cell's 27 nodes, ev
+// [brick][27][4] in FP64. One thread per coarse node sums its <= 8 entries (two cells per direction
+// where the coordinate is a cell boundary) in ascending (Morton brick, local node) order, as
+// k_slab_sum_cube does: deterministic. Rows in the coarse level's vmask are zeroed (the V-cycle's
+// vec_set_indexed over con_dofs, which is what vmask lists on a level without hanging nodes).
+__global__ void __launch_bounds__(256) k_restrict_sum_cube(const double *__restrict__ ev, int nb1, int64_t voff,
+                                                           double *__restrict__ bc, const uint8_t *__restrict__ vmask) {
+  const int NX = 2 * nb1 + 1;
+  int bx = blockIdx.x, Z = blockIdx.y;
+  if (GLS_SLAB_XCD) {
+    const int lin = xcd_swizzle((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
+    bx = lin % (int)gridDim.x;
+    Z = lin / (int)gridDim.x;
+  }
+  const int64_t t = (int64_t)bx * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)NX * NX) return;
+  const int X = (int)(t % NX), Y = (int)(t / NX);
+  int bcd[3][2], lc[3][2], nc[3];
+  const int co[3] = {X, Y, Z};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const int x = co[d];
+    if (x % 2 == 0 && x > 0 && x < NX - 1) {
+      nc[d] = 2;
+      bcd[d][0] = x / 2 - 1;
+      lc[d][0] = 2;
+      bcd[d][1] = x / 2;
+      lc[d][1] = 0;
+    } else {
+      nc[d] = 1;
+      bcd[d][0] = min(x / 2, nb1 - 1);
+      lc[d][0] = x - 2 * bcd[d][0];
+      bcd[d][1] = bcd[d][0];
+      lc[d][1] = lc[d][0];
+    }
+  }
+  int64_t sl[8];
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const bool on = i < nc[0] && j < nc[1] && k < nc[2];
+        const int64_t s = (int64_t)morton3(bcd[0][i], bcd[1][j], bcd[2][k]) * 27 + lc[0][i] + 3 * (lc[1][j] + 3 * lc[2][k]);
+        sl[i + 2 * j + 4 * k] = on ? s : INT64_MAX;
+        cnt += on;
+      }
+  auto cs = [&](int a, int b) {
+    const int64_t lo = min(sl[a], sl[b]), hi = max(sl[a], sl[b]);
+    sl[a] = lo;
+    sl[b] = hi;
+  };
+  cs(0, 1); cs(2, 3); cs(4, 5); cs(6, 7);
+  cs(0, 2); cs(1, 3); cs(4, 6); cs(5, 7);
+  cs(1, 2); cs(5, 6); cs(0, 4); cs(3, 7);
+  cs(1, 5); cs(2, 6);
+  cs(1, 4); cs(3, 6);
+  cs(2, 4); cs(3, 5);
+  cs(3, 4);
+  double e[8][4];
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+    if (q < cnt) SlabQuad<double>::load(ev + sl[q] * 4, e[q][0], e[q][1], e[q][2], e[q][3]);
+  double s[4] = {0., 0., 0., 0.};
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+    if (q < cnt) {
+      s[0] += e[q][0];
+      s[1] += e[q][1];
+      s[2] += e[q][2];
+      s[3] += e[q][3];
+    }
+  const int64_t node = X + (int64_t)NX * (Y + (int64_t)NX * Z);
+  const unsigned m = vmask ? vmask[node] : 0u;
+  bc[node * 3] = (m & 1u) ? 0.0 : s[0];
+  bc[node * 3 + 1] = (m & 2u) ? 0.0 : s[1];
+  bc[node * 3 + 2] = (m & 4u) ? 0.0 : s[2];
+  bc[voff + node] = s[3];
+}
+hipError_t brick_restrict_sum_cube(int nb1, const double *ev, int64_t n_vnodes, double *bc, const uint8_t *vmask,
+                                   hipStream_t s) {
+  const int64_t NX = 2 * (int64_t)nb1 + 1;
+  if (nb1 <= 0 || nb1 > 1023 || !ev || !bc || NX * NX * NX != n_vnodes) return hipErrorInvalidValue;
+  const dim3 g((unsigned)((NX * NX + 255) / 256), (unsigned)NX), b(256);
+  hipLaunchKernelGGL(k_restrict_sum_cube, g, b, 0, s, ev, nb1, 3 * n_vnodes, bc, vmask);
+  return hipGetLastError();
+}
+
 bool brick_fused_jacobi_supported(int k) { return brick_impl(k) == 0 && (k == 1 || k == 2); }
 #ifdef GLS_BRICK_COLORS_BUILD
 bool brick_colors_supported(int k) { return brick_impl(k) == 0 && (k == 1 || k == 2); }

@@ -94,10 +94,15 @@ struct PencilTab {
 // path: their per-point loads and terms cost the residual ~50 VGPRs of spills)
 // FOREST: an FP32 launch on forest bricks (subset list); OS: the Oseen (Picard) operator of the FP32 smoother
 // (MODE_JVQ: no (grad u) v terms, no tau (v . grad phi) R_s term; reads u and tau of the linearization only)
-template <typename Real, int MODE, bool GEN, bool FOREST = false, bool OS = false>
+// RST: the V-cycle's residual restricted in the kernel (FP32 J.v on the cube's bricks): r = own rb - A v of the
+// brick's 125 nodes (own: the one brick that counts the node's rb) is restricted 5 -> 3 per axis in LDS, in FP64,
+// and stored as the brick's coarse element vector [brick][27][4] (P.slab's buffer; summed per coarse node by
+// k_restrict_sum_cube): no y, no slab entries
+template <typename Real, int MODE, bool GEN, bool FOREST = false, bool OS = false, bool RST = false>
 __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_PENCIL_WPE32 : GLS_PENCIL_WPE64))
     gls_pencil_kernel(const OpParams P, const PencilTab<Real> T) {
   static_assert(!OS || (MODE == MODE_JVQ && std::is_same<Real, float>::value), "Oseen operator: FP32 J.v only");
+  static_assert(!RST || (MODE == MODE_JVQ && std::is_same<Real, float>::value && !FOREST), "restriction: FP32 J.v on the cube");
   using C = PencilCfg<Real, MODE == MODE_JVQ>;
   // MODE_RESLIN = MODE_RESIDUAL + MODE_LIN at one state (assemble_matrix_and_rhs); else MODE_JVQ
   constexpr bool RL = MODE == MODE_RESLIN, RES = MODE == MODE_RESIDUAL || RL, LIN = MODE == MODE_LIN || RL;
@@ -400,6 +405,110 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
       e[a * 3 + 1] = (double)o[C::OF];
       e[a * 3 + 2] = (double)o[2 * C::OF];
       e[81 + a] = (double)o[3 * C::OF];
+    }
+  };
+
+  // ---------------- RST: the brick's residual, restricted to its coarse cell (the transposed Q2 interpolation
+  // of the nested level pair, fine brick nodes 0..4 onto coarse cell nodes 0..2 per axis:
+  // c0 = r0 + 3/8 r1 - 1/8 r3, c1 = r2 + 3/4 (r1 + r3), c2 = r4 - 1/8 r1 + 3/8 r3)
+  auto restrict_store = [&]() {
+    auto r53 = [](double r0, double r1, double r2, double r3, double r4, double &c0, double &c1, double &c2) {
+      c0 = r0 + (0.375 * r1 - 0.125 * r3);
+      c1 = r2 + 0.75 * (r1 + r3);
+      c2 = r4 + (0.375 * r3 - 0.125 * r1);
+    };
+    auto compact3 = [](unsigned v) {  // every third bit of a Morton index
+      v &= 0x09249249u;
+      v = (v ^ (v >> 2)) & 0x030c30c3u;
+      v = (v ^ (v >> 4)) & 0x0300f00fu;
+      v = (v ^ (v >> 8)) & 0xff0000ffu;
+      return (int)((v ^ (v >> 16)) & 0x3ffu);
+    };
+    // FP64 from here on (the residual's rb - s and the restriction as the separate FP64 launches form them: the
+    // two paths differ by FP64 summation order only). LDS, all dead by now: r [brick][field][125] and the y
+    // sweep's output in the brick-field + stage areas, the x sweep's output in the cell-value area
+    static_assert((C::BPG * NF * FB + C::WAVES * C::CPW * CS) % 2 == 0 && C::BPG * NF * FB + C::WAVES * C::CPW * CS >= 2 * (C::BPG * 4 * (BN3 + 45)) &&
+                      C::CPG * C::OC >= 2 * C::BPG * 4 * 75, "restriction scratch in LDS");
+    double *const dR = reinterpret_cast<double *>(sB), *const dY = dR + C::BPG * 4 * BN3;
+    double *const dX = reinterpret_cast<double *>(sO);
+    // r of every brick node (cell sums in reduce_scatter's order)
+    for (int t = tid; t < C::BPG * BN3; t += C::THREADS) {
+      const int rb_ = t / BN3, n = t % BN3;
+      if (rb_ >= nbg) break;
+      const int bk = brick_of(rb_);
+      const int Xn = n % BN, Yn = (n / BN) % BN, Zn = n / (BN * BN);
+      Real s[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int kz = 0; kz < 2; ++kz) {
+        const int az = Zn - 2 * kz;
+        if (az < 0 || az > 2) continue;
+#pragma unroll
+        for (int ky = 0; ky < 2; ++ky) {
+          const int ay = Yn - 2 * ky;
+          if (ay < 0 || ay > 2) continue;
+#pragma unroll
+          for (int kx = 0; kx < 2; ++kx) {
+            const int ax = Xn - 2 * kx;
+            if (ax < 0 || ax > 2) continue;
+            const Real *o = sO + (rb_ * 8 + kx + 2 * ky + 4 * kz) * C::OC + ax + 3 * (ay + 3 * az);
+#pragma unroll
+            for (int f = 0; f < 4; ++f) s[f] += o[f * C::OF];
+          }
+        }
+      }
+      const int node = sNode[rb_ * BN3P + n];
+      // a node on a face shared by two bricks belongs to the upper one (local coordinate 0); the domain's
+      // upper faces to their only brick
+      const int top = P.cube_nb1 - 1;
+      const bool own = (Xn < BN - 1 || compact3((unsigned)bk) == top) && (Yn < BN - 1 || compact3((unsigned)bk >> 1) == top) &&
+                       (Zn < BN - 1 || compact3((unsigned)bk >> 2) == top);
+      const unsigned m = P.vmask ? P.vmask[node] : 0u;  // constrained rows restrict onto constrained coarse rows only: 0
+      double r[4] = {-(double)s[0], -(double)s[1], -(double)s[2], -(double)s[3]};
+      if (own) {
+        const int64_t gi[4] = {(int64_t)node * 3, (int64_t)node * 3 + 1, (int64_t)node * 3 + 2, voff + node};
+#pragma unroll
+        for (int f = 0; f < 4; ++f) r[f] = P.rb[gi[f]] - (double)s[f];
+        if (P.jx0) {  // the fused first Jacobi sweep's x (formed in the gather), stored once per node
+#pragma unroll
+          for (int f = 0; f < 4; ++f) P.jx0[gi[f]] = 0.0 + P.jomega * P.rb[gi[f]] / P.jd[gi[f]];
+        }
+      }
+#pragma unroll
+      for (int f = 0; f < 4; ++f) dR[(rb_ * 4 + f) * BN3 + n] = (f < 3 && ((m >> f) & 1u)) ? 0.0 : r[f];
+    }
+    __syncthreads();
+    // x: [brick][field][Y + 5 Z][cx]
+    for (int t = tid; t < nbg * 4 * 25; t += C::THREADS) {
+      const int bf = t / 25, yz = t - bf * 25;
+      const double *r = dR + bf * BN3 + BN * yz;
+      double *o = dX + bf * 75 + 3 * yz;
+      r53(r[0], r[1], r[2], r[3], r[4], o[0], o[1], o[2]);
+    }
+    __syncthreads();
+    // y: [brick][field][cy + 3 Z][cx]
+    for (int t = tid; t < nbg * 4 * 15; t += C::THREADS) {
+      const int bf = t / 15, zx = t - bf * 15, Z = zx / 3, cx_ = zx - 3 * Z;
+      const double *r = dX + bf * 75 + 15 * Z + cx_;
+      double *o = dY + bf * 45 + 9 * Z + cx_;
+      r53(r[0], r[3], r[6], r[9], r[12], o[0], o[3], o[6]);
+    }
+    __syncthreads();
+    // z: one thread per (brick, cx, cy), its three coarse nodes' four fields as two 16-byte stores each
+    for (int t = tid; t < nbg * 9; t += C::THREADS) {
+      const int rb_ = t / 9, xy = t - rb_ * 9;
+      double cv[4][3];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        const double *r = dY + (rb_ * 4 + f) * 45 + xy;
+        r53(r[0], r[9], r[18], r[27], r[36], cv[f][0], cv[f][1], cv[f][2]);
+      }
+      typedef double d2 __attribute__((ext_vector_type(2)));
+      d2 *e = reinterpret_cast<d2 *>(P.slab + ((int64_t)brick_of(rb_) * 27 + xy) * 4);
+#pragma unroll
+      for (int cz_ = 0; cz_ < 3; ++cz_) {
+        e[18 * cz_] = d2{cv[0][cz_], cv[1][cz_]};
+        e[18 * cz_ + 1] = d2{cv[2][cz_], cv[3][cz_]};
+      }
     }
   };
 
@@ -751,8 +860,12 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   }  // MODE_JVQ
   __syncthreads();
 
-  if (P.ev) write_ev();
-  else reduce_scatter(P.y, P.slab, true);
+  if constexpr (RST) {
+    restrict_store();
+  } else {
+    if (P.ev) write_ev();
+    else reduce_scatter(P.y, P.slab, true);
+  }
 }
 
 // (A packed-FP32 variant of the FP32 smoother J.v -- two cells per lane as float2 -- was measured slower than
@@ -805,6 +918,31 @@ hipError_t launch_pencil_jv(const OpParams &P, const Tables1D &T, hipStream_t s,
   if (P.n_probe > 0 || P.bricks || !(f32 ? (P.slabf != nullptr || P.slab != nullptr) : P.slab != nullptr))
     return hipErrorNotSupported;
   return f32 ? launch_pencil_t<float, MODE_JVQ>(P, T, s) : launch_pencil_t<double, MODE_JVQ>(P, T, s);
+}
+// y-less residual of the V-cycle, restricted per brick: rb - A v as coarse element vectors [brick][27][4] in
+// P.slab (P.cube_nb1 bricks per direction, Morton order); P.jx0 as in launch_pencil_jv; no SRF terms
+hipError_t launch_pencil_jv_restrict(const OpParams &P, const Tables1D &T, hipStream_t s) {
+  if (P.n_probe > 0 || P.bricks || P.subset || P.brick_cell0 || P.srf || !P.slab || !P.rb || !P.qdf || P.jx || (P.jx0 && !P.jd) ||
+      P.cube_nb1 <= 0 || (int64_t)P.cube_nb1 * P.cube_nb1 * P.cube_nb1 * 8 != P.n_cells)
+    return hipErrorNotSupported;
+  const int n_groups = (P.n_cells / 8 + 2) / 3;
+  PencilTab<float> tab;
+  for (int q = 0; q < 3; ++q) {
+    tab.w[q] = (float)T.w[q];
+    for (int i = 0; i < 3; ++i) {
+      tab.V[q][i] = (float)T.V[q][i];
+      tab.D[q][i] = (float)T.D[q][i];
+      tab.S[q][i] = (float)T.S[q][i];
+    }
+    tab.xi[q] = (float)T.xi[q];
+  }
+  if (P.oseen)
+    hipLaunchKernelGGL((gls_pencil_kernel<float, MODE_JVQ, false, false, true, true>), dim3((unsigned)n_groups), dim3(256),
+                       pencil_lds_bytes<float>(MODE_JVQ), s, P, tab);
+  else
+    hipLaunchKernelGGL((gls_pencil_kernel<float, MODE_JVQ, false, false, false, true>), dim3((unsigned)n_groups), dim3(256),
+                       pencil_lds_bytes<float>(MODE_JVQ), s, P, tab);
+  return hipGetLastError();
 }
 hipError_t launch_pencil_residual(const OpParams &P, const Tables1D &T, hipStream_t s) {
   if (P.bricks || !P.slab || P.subset) return hipErrorNotSupported;

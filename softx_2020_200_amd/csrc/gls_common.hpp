@@ -117,6 +117,7 @@ struct OpParams {
   // with the same code)
   double *cq;
   int cq_mode;
+  int cube_nb1;               // pencil J.v with the in-kernel restriction: bricks per direction of the hyper_cube
 };
 
 }  // namespace gls

@@ -26,6 +26,10 @@ hipError_t vec_from_f32(const float *a, double *b, int64_t n, hipStream_t s);
 // contract as the lane-per-point MODE_JVQ launch with a slab; hipErrorNotSupported when not applicable
 // (probing, colored launches, no slab). GLS_PENCIL=0 disables it.
 hipError_t launch_pencil_jv(const OpParams &P, const Tables1D &T, hipStream_t s, bool f32);
+// FP32 J.v of the V-cycle's residual with the restriction to the next-coarser nested level inside the
+// kernel (hyper_cube, Morton bricks): rb - A v per brick, restricted 5 -> 3 per axis, as coarse element
+// vectors [brick][27][4] (FP64) in P.slab's buffer; nothing goes to y. hipErrorNotSupported when not applicable
+hipError_t launch_pencil_jv_restrict(const OpParams &P, const Tables1D &T, hipStream_t s);
 hipError_t launch_pencil_residual(const OpParams &P, const Tables1D &T, hipStream_t s);  // MODE_RESIDUAL, FP64
 hipError_t launch_pencil_lin(const OpParams &P, const Tables1D &T, hipStream_t s);  // MODE_LIN (+ diagonal into P.y)
 // MODE_RESLIN: residual (res_y / res_slab) + linearization (qd, qdf) + diagonal (y / slab) in one pass
@@ -53,6 +57,11 @@ hipError_t brick_slab_sum_ex(const double *slab, const float *slabf, const int32
 hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *slabf, int64_t n_vnodes, double *y,
                                const uint8_t *vmask, const double *jb, const double *jd, double jomega, hipStream_t s,
                                const double *rb = nullptr, double *x0 = nullptr);  // x0: OpParams::jx0's surface nodes
+// coarse right-hand side from the bricks' restricted residuals (launch_pencil_jv_restrict: ev [brick][27][4],
+// nb1 fine bricks = coarse cells per direction): bc[node] = sum of the node's <= 8 element-vector entries in
+// ascending (Morton brick, local node) order, rows in the coarse vmask zeroed; n_vnodes = (2 nb1 + 1)^3
+hipError_t brick_restrict_sum_cube(int nb1, const double *ev, int64_t n_vnodes, double *bc, const uint8_t *vmask,
+                                   hipStream_t s);
 bool brick_fused_jacobi_supported(int k);  // the selected brick kernel honours OpParams::jx and ::slabf
 // batched probing: Y[(j - j0) * n_dofs + i] += (J_cell-sum e_j)_i for nprobe unit vectors (MODE_JVQ)
 bool brick_colors_supported(int k);  // colored brick launches (OpParams::bricks) available

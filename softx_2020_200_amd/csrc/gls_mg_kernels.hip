@@ -7,6 +7,11 @@
 // on the host), velocity and pressure together; the one-pass 125-tap gather remains for lattices
 // whose tiles do not fit (it reads the fine vector once but is load-issue bound: 0.45 / 0.72 ms
 // for the 128^3 restriction / prolongation).
+// Not every restriction comes through here: on one rank, a level that smooths in FP32 on the cube's Q2
+// bricks restricts its residual inside the smoother's J.v (a brick is one coarse cell: the RST
+// instantiation of gls_pencil_kernel, gls_brick_pencil.hip) and sums the bricks' coarse element vectors
+// with k_restrict_sum_cube (gls_brick_kernels.hip); gls_mg_attach checks these tap tables against that
+// kernel's closed form. The prolongation and every other hierarchy use the kernels below.
 // Multi-GPU: each rank works on the box sub-lattice its cells span (box gather / scatter through
 // a box -> local node map); nested partitions keep the coarse box the fine box's every-second node.
 #include "gls_launch.hpp"

@@ -32,6 +32,7 @@ EXPORTS = [
     "gls_part_create", "gls_part_sizes", "gls_part_get", "gls_part_destroy", "gls_dist_attach", "gls_dist_import", "gls_rccl_unique_id", "gls_rccl_create", "gls_rccl_destroy", "gls_rccl_info", "gls_mg_smoother_apply", "gls_mg_attach_replica",
     "gls_dist_attach_rccl",
     "gls_mg_attach", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
+    "gls_mg_residual_restrict",
     "gls_prm_parse", "gls_prm_get", "gls_prm_n_entries", "gls_prm_entry", "gls_prm_destroy",
     "gls_expr_create", "gls_expr_n_components", "gls_expr_eval", "gls_expr_destroy",
     "gls_vtu_write", "gls_pvtu_write", "gls_pvd_write",
@@ -182,6 +183,7 @@ def load():
     L.gls_mg_attach_replica.argtypes = [vp, C.POINTER(MGParams), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.gls_mg_transfer.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.gls_mg_residual_restrict.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
     P64 = C.POINTER(i64)
     L.gls_set_hanging.argtypes = [vp, i64, P64, P64, P64, d]
     L.gls_mesh_refined_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
@@ -898,6 +900,15 @@ class GLSContext:
         """Restrict (direction 0: level -> level+1) or prolongate (1: level+1 -> level) a device vector."""
         check(self.L.gls_mg_transfer(self.h, int(level), int(direction), _ptr(v), _ptr(out)), "gls_mg_transfer")
         return out
+
+    def mg_residual_restrict(self, level, x, b, out):
+        """The V-cycle's coarse right-hand side of level+1 from level's iterate x and right-hand side b,
+        out = R (b - A_s x) with constrained rows zeroed (gls_mg_residual_restrict). Returns (out, fused):
+        fused is True when the in-kernel restriction ran, False for the separate launches."""
+        fused = C.c_int(0)
+        check(self.L.gls_mg_residual_restrict(self.h, int(level), _ptr(x), _ptr(b), _ptr(out), C.byref(fused)),
+              "gls_mg_residual_restrict")
+        return out, bool(fused.value)
 
     def set_lattice(self, n1d, local_to_global):
         """Declare the (rank-local) nodes as a box of the global n1d^3 hyper_cube node lattice."""

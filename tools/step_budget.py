@@ -66,8 +66,10 @@ def classify(name, blocks, threads, n_fine):
         if "<float, 4" in nm or pair:
             return ("smoother J.v FP32 fine" if n == n_fine else "smoother J.v FP32 coarse levels"), n, b_jv(n)
         return "brick kernel (other)", n, 0
-    if "k_slab_sum" in nm:
-        return "slab sums", None, 0  # folded into their J.v's algorithmic bytes (the J.v's y write)
+    if "k_slab_sum" in nm or "k_restrict_sum" in nm:
+        # folded into their J.v's algorithmic bytes (the J.v's y write; k_restrict_sum_cube: the coarse right-hand
+        # side of the residual J.v with the in-kernel restriction, gls_pencil_kernel<float, 4, ..., true>)
+        return "slab sums", None, 0
     m = re.search(r"k_multidot(?:16)?<(\d+)", nm)
     if m:
         return "GMRES orthogonalisation", None, (int(m.group(1)) + 1) * 8 * Nf
