@@ -2,8 +2,10 @@
 // for the reference's applications/gls_navier_stokes_{2d,3d} (the GLSNavierStokesSolver::solve
 // flow, gls_navier_stokes.cc:1395-1423), built only on the C-ABI of libgls_native.so:
 //   read prm (gls_prm_*) -> hyper_cube mesh + boundary conditions (setup_dofs :55-228) ->
-//   initial condition (nodal | L2projection | viscous, :784-827) -> time loop (integrate, first
-//   step with the BDF start-up, SDIRK stages; navier_stokes_base.cc:426-590) with the device
+//   initial condition (nodal | L2projection | viscous, :784-827) -> time loop (integrate of the
+//   library's simulation control, gls_time_control_*: constant or CFL-adaptive steps, output by
+//   iteration or by time; first step with the BDF start-up, SDIRK stages;
+//   navier_stokes_base.cc:426-590) with the device
 //   Newton/GMRES (gls_newton_solve) -> post-processing (L2 error vs the analytical solution,
 //   enstrophy, kinetic energy, CFL; forces and torques on the boundaries from the device-resident
 //   solution, `forces` section: log tables and <name>.<NN>.dat; VTU/PVTU/PVD output).
@@ -148,6 +150,10 @@ struct Params {
   double dt = 1.0, t_end = 1.0, startup = 0.4;
   int mesh_adapt = 0, output_frequency = 1, subdivision = 1, log_frequency = 1;
   int adapt_frequency = 1;  // mesh adaptation/frequency (refine_mesh: step % frequency == 0)
+  // adaptive time stepping and time-controlled output (parameters.cc:27-43, 64-71, 109-123)
+  bool adapt = false;
+  double max_cfl = 1.0, dt_scaling = 1.1, output_time = 1.0;
+  int output_control = GLS_OUTPUT_ITERATION;
   std::string output_path = "./", output_name = "out";
   double nu = 1.0;
   int k = 1, kp = 1;
@@ -219,7 +225,14 @@ Params read_params(const Prm &p, int dim) {
   P.subdivision = p.i(sc + "subdivision", 1);
   P.output_path = p.get(sc + "output path", "./");
   P.output_name = p.get(sc + "output name", "out");
-  if (p.b(sc + "adapt", false)) die("adaptive time stepping is not supported");
+  P.adapt = p.b(sc + "adapt", false);
+  P.max_cfl = p.d(sc + "max cfl", 1.0);
+  P.dt_scaling = p.d(sc + "adaptative time step scaling", 1.1);
+  P.output_time = p.d(sc + "output time", 1.0);
+  const std::string oc = p.get(sc + "output control", "iteration");
+  if (oc == "iteration") P.output_control = GLS_OUTPUT_ITERATION;
+  else if (oc == "time") P.output_control = GLS_OUTPUT_TIME;
+  else die("output control '%s' is unknown (iteration | time)", oc.c_str());
   P.nu = p.d("physical properties/kinematic viscosity", 1.0);
   P.k = p.i("FEM/velocity order", 1);
   P.kp = p.i("FEM/pressure order", 1);
@@ -396,39 +409,6 @@ Params read_params(const Prm &p, int dim) {
   P.omega[1] = p.d("velocity source/omega_y", 0.);
   P.omega[2] = p.d("velocity source/omega_z", 0.);
   return P;
-}
-
-// ---------------------------------------------------------------------------------------------
-// device CFL on box cells (calculate_CFL: |u| at the cell centre * dt / h_cell, h_cell =
-// (6|K|/pi)^(1/3) / degree, 2D sqrt(4|K|/pi) / degree): one thread per cell, per-block maxima
-// ---------------------------------------------------------------------------------------------
-__global__ void k_cfl(const int32_t *cv, const double *h, const double *u, int64_t nc, int dim, int nvl, int k1,
-                      double b0, double b1, double b2, double deg, double dt, double *blockmax) {
-  __shared__ double red[256];
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  double v = 0.0;
-  if (c < nc) {
-    const double B[3] = {b0, b1, b2};
-    double uc[3] = {0, 0, 0}, meas = 1.0;
-    for (int a = 0; a < nvl; ++a) {
-      const int ax = a % k1, ay = (a / k1) % k1, az = a / (k1 * k1);
-      const double w = B[ax] * B[ay] * (dim == 3 ? B[az] : 1.0);
-      const int64_t node = cv[c * nvl + a];
-      for (int d = 0; d < dim; ++d) uc[d] += w * u[node * dim + d];
-    }
-    for (int d = 0; d < dim; ++d) meas *= h[c * dim + d];
-    const double hh = dim == 2 ? sqrt(4. * meas / M_PI) / deg : cbrt(6. * meas / M_PI) / deg;
-    double un = 0;
-    for (int d = 0; d < dim; ++d) un += uc[d] * uc[d];
-    v = sqrt(un) / hh * dt;
-  }
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + st]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) blockmax[blockIdx.x] = red[0];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1124,11 +1104,11 @@ struct Solver {
   double *d_present = nullptr, *d_m1 = nullptr, *d_m2 = nullptr, *d_m3 = nullptr;
   std::vector<double> present, m1, m2, m3;
   // The time loop is device-resident: between solves the state and history live in d_* (history
-  // shift = pointer rotation + one device copy, CFL on the device for box meshes); the host copies
-  // are refreshed only for output, post-processing, mesh adaptation and initial conditions.
+  // shift = pointer rotation + one device copy; CFL, kinetic energy and enstrophy in one device pass,
+  // gls_flow_diagnostics); the host copies are refreshed only for output, the L2 error, mesh adaptation
+  // and initial conditions.
   bool dev_ok = false, host_ok = true;  // which side holds the current state
-  int32_t *d_cv = nullptr;              // box meshes: cell -> velocity node map and extents (device CFL)
-  double *d_h = nullptr, *d_blk = nullptr;
+  gls_time_control *tc = nullptr;       // transient runs: iteration, time and step (simulation_control.cc)
   int step = 0;
   double time = 0.0, dt_now = 0.0, cfl = 0.0;
   double dts[4] = {0, 0, 0, 0};  // time steps, most recent first (BDF coefficients)
@@ -1178,6 +1158,7 @@ struct Solver {
     if (space) gls_fe_space_destroy(space);
     if (um) gls_umesh_destroy(um);
     if (tree) gls_octree_destroy(tree);
+    if (tc) gls_time_control_destroy(tc);
   }
 
   void release() {
@@ -1192,10 +1173,7 @@ struct Solver {
     loc.xchg.reset();  // the transport outlives its context
     if (rmesh) gls_octree_mesh_destroy(rmesh);
     rmesh = nullptr;
-    if (d_cv) (void)hipFree(d_cv);
-    for (double *q : {d_h, d_blk}) if (q) (void)hipFree(q);
-    d_cv = nullptr;
-    d_h = d_blk = nullptr;
+    diag_valid = false;  // the diagnostics belong to the context's mesh
     for (double *q : {d_present, d_m1, d_m2, d_m3})
       if (q) (void)hipFree(q);
     d_present = d_m1 = d_m2 = d_m3 = nullptr;
@@ -2338,8 +2316,42 @@ struct Solver {
     }
     return {std::sqrt(eu), std::sqrt(ep)};
   }
+  // CFL (at step dt_now), int 0.5|u|^2, int 0.5|curl u|^2 and the volume of the present solution: one device
+  // pass per iteration over d_present (gls_flow_diagnostics), shared by end_of_step() and postprocess() like
+  // the boundary loads. --np: every rank's own cells on its local context (ghost values refreshed by one
+  // neighbour exchange), the four numbers combined through the shared-memory communicator: the maximum of
+  // the CFL, the sums in rank order.
+  double diag[4] = {0, 0, 0, 0};
+  bool diag_valid = false;
+  int diag_step = -1;
+  bool diag_on_device() const { return m.k <= 2 && m.kp <= m.k; }
+  void flow_diagnostics() {
+    if (diag_valid && diag_step == step) return;
+    need_dev();
+    if (world > 1) ck(gls_dist_import(ctx, d_present), "gls_dist_import");
+    ck(gls_flow_diagnostics(ctx, d_present, dt_now, diag), "gls_flow_diagnostics");
+    if (world > 1) {
+      std::memcpy(g_comm.slot(rank), diag, sizeof(diag));
+      g_comm.barrier("diagnostics");
+      double r[4] = {0, 0, 0, 0};
+      for (int q = 0; q < world; ++q) {
+        const double *v = g_comm.slot(q);
+        r[0] = std::max(r[0], v[0]);
+        for (int i = 1; i < 4; ++i) r[i] += v[i];
+      }
+      g_comm.barrier("diagnostics-done");
+      std::memcpy(diag, r, sizeof(diag));
+    }
+    diag_valid = true;
+    diag_step = step;
+  }
   // volume averages with QGauss(k+1): 0.5|curl u|^2 (enstrophy) or 0.5|u|^2 (kinetic energy)
   double volume_average(bool enstrophy) {
+    if (diag_on_device()) {
+      flow_diagnostics();
+      return diag[enstrophy ? 2 : 1] / diag[3];
+    }
+    need_host();
     CellEval ev(m, std::max(m.k, m.kp) + 1);
     double s = 0, vol = 0;
     for (int64_t c = 0; c < m.nc; ++c)
@@ -2361,29 +2373,9 @@ struct Solver {
       }
     return s / vol;
   }
-  // CFL from the velocity at the cell centre and h = (6|K|/pi)^(1/3)/k (3D), sqrt(4|K|/pi)/k (2D)
+  // CFL from the velocity at the cell centre and h = (6|K|/pi)^(1/3)/k (3D), sqrt(4|K|/pi)/k (2D): the host
+  // pass, for the degrees without a device kernel (2D Q3)
   double compute_cfl(double dt) {
-    if (!m.general && m.vx.empty() && m.k <= 2) {  // box cells: on the device, from d_present
-      const int k1 = m.k + 1, nvl = m.dim == 3 ? k1 * k1 * k1 : k1 * k1;
-      const int64_t nb = (m.nc + 255) / 256;
-      if (!d_cv) {
-        hk(hipMalloc(&d_cv, sizeof(int32_t) * m.cv.size()), "hipMalloc");
-        hk(hipMalloc(&d_h, sizeof(double) * m.h.size()), "hipMalloc");
-        hk(hipMalloc(&d_blk, sizeof(double) * (size_t)nb), "hipMalloc");
-        hk(hipMemcpy(d_cv, m.cv.data(), sizeof(int32_t) * m.cv.size(), hipMemcpyHostToDevice), "upload");
-        hk(hipMemcpy(d_h, m.h.data(), sizeof(double) * m.h.size(), hipMemcpyHostToDevice), "upload");
-      }
-      need_dev();
-      double b[3] = {0, 0, 0}, db[4];
-      lag1d(lobatto01(m.k), 0.5, b, db);
-      hk(hipDeviceSynchronize(), "cfl");
-      hipLaunchKernelGGL(k_cfl, dim3((unsigned)nb), dim3(256), 0, 0, d_cv, d_h, d_present, m.nc, m.dim, nvl, k1, b[0], b[1],
-                         b[2], (double)std::max(m.k, m.kp), dt, d_blk);
-      hk(hipGetLastError(), "k_cfl");
-      std::vector<double> bm((size_t)nb);
-      hk(hipMemcpy(bm.data(), d_blk, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost), "download");
-      return *std::max_element(bm.begin(), bm.end());
-    }
     need_host();
     CellEval ev(m, 1);
     const int deg = std::max(m.k, m.kp);
@@ -2441,8 +2433,15 @@ struct Solver {
        "gls_pvd_write");
   }
   void postprocess(bool initial) {
-    if (P.output_frequency > 0 && step % P.output_frequency == 0) write_output();
-    if (P.enstrophy || P.kinetic || (!initial && P.analytical)) need_host();
+    // output control = time: the controller decides (and records the output time: once per iteration)
+    if (tc && P.output_control == GLS_OUTPUT_TIME) {
+      const int r = gls_time_control_is_output_iteration(tc);
+      ck(r, "gls_time_control_is_output_iteration");
+      if (r == 1) write_output();
+    } else if (P.output_frequency > 0 && step % P.output_frequency == 0) {
+      write_output();
+    }
+    if (!initial && P.analytical) need_host();
     // post-processing lines of NavierStokesBase::postprocess (navier_stokes_base.cc:791-853)
     if (P.enstrophy && P.pp_verbose) std::printf("Enstrophy  : %s\n", g6(volume_average(true)).c_str());
     if (P.kinetic) {  // navier_stokes_base.cc:824-839
@@ -2479,7 +2478,13 @@ struct Solver {
     d_m1 = t;
     dcopy(d_m1, d_present);
     dev_changed();
-    cfl = compute_cfl(dt_now);
+    if (diag_on_device()) {
+      flow_diagnostics();
+      cfl = diag[0];
+    } else {
+      cfl = compute_cfl(dt_now);
+    }
+    if (tc) ck(gls_time_control_set_cfl(tc, cfl), "gls_time_control_set_cfl");
   }
   // uniform refinement with interpolation of the Qk fields onto the refined lattice
   void refine_uniform() {
@@ -3038,17 +3043,36 @@ struct Solver {
     } else {
       die("initial condition type '%s' is not supported", P.ic_type.c_str());
     }
+    const bool steady = P.method == Method::steady;
+    if (!steady) {  // SimulationControlTransient / ...DynamicOutput (simulation_control.cc:84-218)
+      gls_time_control_params tp;
+      std::memset(&tp, 0, sizeof(tp));
+      tp.dt = P.dt;
+      tp.time_end = P.t_end;
+      tp.adapt = P.adapt ? 1 : 0;
+      tp.max_cfl = P.max_cfl;
+      tp.scaling = P.dt_scaling;
+      tp.output_control = P.output_control;
+      tp.output_frequency = std::max(P.output_frequency, 1);
+      tp.output_time = P.output_time;
+      ck(gls_time_control_create(&tp, &tc), "simulation control");
+    }
     end_of_step();
     postprocess(true);
-    const bool steady = P.method == Method::steady;
-    while (steady ? step < P.mesh_adapt + 1 : time < P.t_end - 1e-12 * dt_now) {
-      ++step;
+    auto next_iteration = [&]() {  // integrate(): false at the end of the simulation
+      if (steady) return step < P.mesh_adapt + 1;
+      const int r = gls_time_control_integrate(tc);
+      ck(r, "gls_time_control_integrate");
+      return r == 1;
+    };
+    while (next_iteration()) {
       if (steady) {
+        ++step;
         time = step;
       } else {
-        const double dt = std::min(dt_now, P.t_end - time);
+        double dt = 0.0;
+        ck(gls_time_control_get(tc, &step, &time, &dt, nullptr), "gls_time_control_get");
         push_dt(dt);
-        time += dt;
       }
       if (P.log_frequency > 0 && step % P.log_frequency == 0) {
         // SimulationControl{Steady,Transient}::print_progression (simulation_control.cc:92-107, 242-255)

@@ -178,8 +178,7 @@ typedef struct {
   double final_residual;  /* out */
   int method;             /* GLS_LIN_GMRES (0, default) | GLS_LIN_BICGSTAB ('linear solver/method',
                              parameters.cc:519-532; 'amg' is GMRES with the caller's preconditioner) */
-  int orthogonalization;  /* GMRES only: GLS_ORTHO_GRAM (0) | GLS_ORTHO_CGS2; the environment variable
-                             GLS_GMRES_CGS2=1 forces CGS2 for every call */
+  int orthogonalization;  /* GMRES only: GLS_ORTHO_GRAM (0) | GLS_ORTHO_CGS2 */
   int true_residual;      /* in: 1 = on convergence recompute ||b - A x|| into final_residual (one extra
                              operator application); 0 = the Krylov recurrence estimate (deal.II) */
 } gls_linear_params;
@@ -498,6 +497,41 @@ int gls_dist_attach_dofs_rccl(gls_ctx *ctx, gls_rccl *comm, int64_t n_owned_vnod
 int gls_bdf_coefficients(int order, const double *dt, int n_dt, double *alpha);
 /* sdirk_coefficients (source/core/sdirk.cc:11-44): out[order*(order+1)] row-major */
 int gls_sdirk_coefficients(int order, double dt, double *out);
+/* Transient simulation control: SimulationControlTransient (source/core/simulation_control.cc:84-147) and,
+ * with output_control = GLS_OUTPUT_TIME, SimulationControlTransientDynamicOutput (:173-218). Parameters
+ * are the 'simulation control' entries 'time step', 'time end', 'adapt', 'max cfl', 'adaptative time step
+ * scaling', 'output control', 'output frequency', 'output time' (parameters.cc:27-71, 109-131).
+ *   gls_time_control_integrate: integrate() (:109-122) -- returns 0 at the end (time >= time_end -
+ *     1e-12 * step, :126-130), else increments the iteration, takes the next step, shifts the four stored
+ *     steps (newest first, add_time_step :28-38) and advances the time; returns 1.
+ *   The next step, calculate_time_step (:132-147): the present step; with adapt from iteration 2 on
+ *     step * scaling, or step * max_cfl / CFL when CFL > 0 and max_cfl / CFL < scaling; then clamped to
+ *     land on time_end. GLS_OUTPUT_TIME (:180-206; the reference's class scales the step whatever 'adapt'
+ *     says, and so does this one): the step is also clamped to land on the next multiple of output_time
+ *     (a forced output step), and the step after a forced one is the step before it (steps[1]) again.
+ *   gls_time_control_set_cfl: set_CFL, the CFL of the iteration just solved (gls_flow_diagnostics' out[0]).
+ *   gls_time_control_is_output_iteration: GLS_OUTPUT_ITERATION iteration % output_frequency == 0 (:40-44);
+ *     GLS_OUTPUT_TIME (:208-218) time - last output time > output_time (1 - 1e-12), and the last output
+ *     time then becomes the present time: a side effect, as in the reference -- call it once per iteration.
+ *   gls_time_control_get: iteration, time, step, the four stored steps (any pointer may be NULL).
+ * With adapt off and GLS_OUTPUT_ITERATION the step is constant but for the final clamp. Host only. */
+#define GLS_OUTPUT_ITERATION 0
+#define GLS_OUTPUT_TIME 1
+typedef struct {
+  double dt, time_end;
+  int adapt;
+  double max_cfl, scaling;
+  int output_control;     /* GLS_OUTPUT_ITERATION | GLS_OUTPUT_TIME */
+  int output_frequency;   /* GLS_OUTPUT_ITERATION: >= 1 */
+  double output_time;     /* GLS_OUTPUT_TIME: > 0 */
+} gls_time_control_params;
+typedef struct gls_time_control gls_time_control;
+int gls_time_control_create(const gls_time_control_params *prm, gls_time_control **out);
+void gls_time_control_destroy(gls_time_control *tc);
+int gls_time_control_integrate(gls_time_control *tc);
+int gls_time_control_set_cfl(gls_time_control *tc, double cfl);
+int gls_time_control_get(const gls_time_control *tc, int *iteration, double *time, double *time_step, double steps[4]);
+int gls_time_control_is_output_iteration(gls_time_control *tc);
 /* Newton driver KAT: the reference's fake physics x0^2+x1=0, 2x1+3=0
  * (tests/core/non_linear_test_system_01.h:50-129) through the same Newton template. */
 int gls_newton_selftest(double x_out[2]);
@@ -627,6 +661,23 @@ int gls_boundary_plan_create(gls_ctx *ctx, int64_t n_faces, int nqf, const int32
 int gls_boundary_plan_destroy(gls_boundary_plan *plan);
 int gls_boundary_loads(gls_ctx *ctx, gls_boundary_plan *plan, const double *sol, double viscosity, const double *cor,
                        double *force, double *torque);
+/* Flow diagnostics of a solution vector in one pass over the context's cells, on the DEVICE (sol: the
+ * context's layout, constrained DoFs holding their values as after gls_apply_dirichlet):
+ *   out[0] = max over cells of |u(centre)| dt / h: calculate_CFL (postprocessing_cfl.cc:36-87) -- the velocity
+ *            at the reference cell's centre, h = sqrt(4|K|/pi)/deg (2D), (6|K|/pi)^(1/3)/deg (3D), deg =
+ *            max(k, kp), |K| = cell->measure() (box cells: the product of cell_h; mapped cells: from the
+ *            corner support points);
+ *   out[1] = int 1/2 |u|^2, out[2] = int 1/2 |curl u|^2 (2D: omega_z only), out[3] = sum of JxW, with the
+ *            context's QGauss(k+1) and its JxW / J^-1 per quadrature point (calculate_kinetic_energy,
+ *            postprocessing_kinetic_energy.cc, and calculate_enstrophy, postprocessing_enstrophy.cc, divide
+ *            out[1], out[2] by the volume).
+ * Every layout of a context: brick, per-cell box, mapped, with hanging lines; a distributed context sums its
+ * own cells (ghost values of sol must be current: gls_dist_import), the caller combines the ranks.
+ * Per-block partials, then one ordered stage on the device: no atomics, two calls on the same input are
+ * bitwise equal. The work is queued on the context's stream; the buffers are allocated at the first call;
+ * out (HOST) is one download of 4 doubles. Kernels exist for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}
+ * with QGauss(k+1); other degrees (2D Q3) are GLS_EINVAL. */
+int gls_flow_diagnostics(gls_ctx *ctx, const double *sol, double dt, double out[4]);
 /* GridRefinement::refine_and_coarsen_fixed_number, refinement part (navier_stokes_base.cc:654-661;
  * serial deal.II rule): flags[i] = 1 for the int(top_fraction * n_cells) largest criteria (every
  * cell >= the threshold value). Returns the number of flagged cells. HOST arrays. */

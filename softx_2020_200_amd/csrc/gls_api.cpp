@@ -277,6 +277,8 @@ struct gls_ctx {
   DevBuf<int32_t> face_nbr;  // [n_cells][2 dim] face neighbours (Kelly), built on first use
   DevBuf<double> geo, x0, force_q;
   DevBuf<double> gq;               // mapped cells: per-q geometry [n_cells][nq][kGeo] (nullptr: boxes)
+  // gls_flow_diagnostics, allocated at its first call: cell->measure(), the 1D tables, block partials, result
+  DevBuf<double> fd_meas, fd_tab, fd_partial, fd_out;
   std::vector<double> host_x0, host_h, host_support;  // host geometry for gls_quadrature_points
   int map_degree = 0;
   DevBuf<uint8_t> vmask;
@@ -3679,6 +3681,51 @@ int gls_boundary_loads(gls_ctx *c, gls_boundary_plan *p, const double *sol, doub
       force[3 * s + i] = o[(size_t)(6 * s + i)];
       torque[3 * s + i] = o[(size_t)(6 * s + 3 + i)];
     }
+  return GLS_OK;
+}
+
+// --------------------------------------------------------------------------------------------
+// Flow diagnostics (postprocessing_cfl.cc, postprocessing_kinetic_energy.cc, postprocessing_enstrophy.cc):
+// one pass over the context's cells, per-block partials and one ordered stage on the device
+// --------------------------------------------------------------------------------------------
+int gls_flow_diagnostics(gls_ctx *c, const double *sol, double dt, double out[4]) {
+  GLS_TRY(check_ctx(c));
+  if (!sol || !out) return set_err(GLS_EINVAL, "gls_flow_diagnostics: bad arguments");
+  if (!gls::flow_diagnostics_supported(c->dim, c->k, c->kp) || c->nq1d != c->k + 1)
+    return set_err(GLS_EINVAL,
+                   "gls_flow_diagnostics: FE_Q(%d)-FE_Q(%d) in %dD with QGauss(%d) has no diagnostics kernel (velocity / "
+                   "pressure orders (1,1), (2,1), (2,2) with QGauss(k+1); 2D Q3 is not supported)",
+                   c->k, c->kp, c->dim, c->nq1d);
+  for (int i = 0; i < 4; ++i) out[i] = 0.0;
+  if (c->n_cells == 0) return GLS_OK;
+  if (!c->fd_out.p) {  // once per context: cell measures, 1D tables, partials
+    const int dim = c->dim, k1 = c->k + 1;
+    std::vector<double> meas((size_t)c->n_cells, 1.0);
+    if (c->map_degree > 0) {
+      const size_t nsup = (size_t)gls::ipow(c->map_degree + 1, dim);
+      for (int cix = 0; cix < c->n_cells; ++cix)
+        meas[(size_t)cix] = corner_measure(dim, c->map_degree, c->host_support.data() + (size_t)cix * nsup * dim);
+    } else {
+      for (int cix = 0; cix < c->n_cells; ++cix)
+        for (int e = 0; e < dim; ++e) meas[(size_t)cix] *= c->host_h[(size_t)cix * dim + e];
+    }
+    std::vector<double> tab((size_t)(2 * k1 * k1 + k1));
+    for (int q = 0; q < k1; ++q) {
+      for (int a = 0; a < k1; ++a) {
+        tab[(size_t)(q * k1 + a)] = c->tables.V[q][a];
+        tab[(size_t)(k1 * k1 + q * k1 + a)] = c->tables.D[q][a];
+      }
+      tab[(size_t)(2 * k1 * k1 + q)] = c->tables.w[q];
+    }
+    GLS_TRY(c->fd_meas.upload(meas.data(), meas.size()));
+    GLS_TRY(c->fd_tab.upload(tab.data(), tab.size()));
+    GLS_TRY(c->fd_partial.alloc((size_t)gls::flow_diagnostics_blocks(c->n_cells) * 4));
+    GLS_TRY(c->fd_out.alloc(4));
+  }
+  HIP_TRY(gls::launch_flow_diagnostics(c->dim, c->k, c->cell_vnodes.p, c->geo.p, c->gq.p, c->fd_meas.p, c->fd_tab.p, sol,
+                                       c->n_cells, dt, c->fd_partial.p, c->fd_out.p, c->stream));
+  HIP_TRY(hipMemcpyAsync(out, c->fd_out.p, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return GLS_OK;
 }
 

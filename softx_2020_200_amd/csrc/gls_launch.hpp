@@ -207,6 +207,17 @@ hipError_t launch_boundary_loads(int dim, int k, int kp, const int32_t *cell_vno
                                  const double *jxw, const double *xq, double nu, const double *cor, int n_slots,
                                  double *partial, double *out, hipStream_t s);
 
+// ---- flow diagnostics (gls_diagnostics.hip): CFL maximum, int 1/2 |u|^2, int 1/2 |curl u|^2 and the volume in
+// one pass, one lane per cell, QGauss(k+1). geo [n_cells][4] (box extents), gq [n_cells][nq][kGeo] (mapped
+// cells; nullptr: boxes), meas [n_cells] = cell->measure(), tab = V [k+1][k+1] | D [k+1][k+1] | w [k+1] (1D
+// velocity basis values / derivatives [q][node] and Gauss weights). partial: flow_diagnostics_blocks(n_cells)
+// * 4 doubles; out [4], folded in a fixed order (bitwise reproducible). Instantiated for dim 2, 3 and k 1, 2.
+int64_t flow_diagnostics_blocks(int64_t n_cells);
+bool flow_diagnostics_supported(int dim, int k, int kp);
+hipError_t launch_flow_diagnostics(int dim, int k, const int32_t *cell_vnodes, const double *geo, const double *gq,
+                                   const double *meas, const double *tab, const double *sol, int64_t n_cells, double dt,
+                                   double *partial, double *out, hipStream_t s);
+
 // ---- geometric multigrid (gls_mg_kernels.hip): nested Qk node lattices (boxes), k <= 2
 hipError_t mg_inject(const double *fine, double *coarse, const int nf[3], const int nc[3], hipStream_t s);
 // one-pass 3D transfer with per-axis tap tables [n_out][5] (index, weight) and tap counts [n_out]

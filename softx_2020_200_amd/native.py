@@ -47,6 +47,8 @@ EXPORTS = [
     "gls_octree_coarsen_to", "gls_octree_mg_transfer", "gls_mg_attach_transfers", "gls_umesh_coarsen_to",
     "gls_fe_space_mg_transfer", "gls_forest_bricks",
     "gls_fe_space_boundary_faces", "gls_boundary_plan_create", "gls_boundary_plan_destroy", "gls_boundary_loads",
+    "gls_flow_diagnostics", "gls_time_control_create", "gls_time_control_destroy", "gls_time_control_integrate",
+    "gls_time_control_set_cfl", "gls_time_control_get", "gls_time_control_is_output_iteration",
 ]
 
 
@@ -98,6 +100,15 @@ class MGParams(C.Structure):
                 ("post_smooth", C.c_int), ("coarse_sweeps", C.c_int), ("omega", C.c_double),
                 ("coarse_omega", C.c_double), ("coarse_direct", C.c_int), ("mixed_precision", C.c_int),
                 ("level_sweeps", C.POINTER(C.c_int)), ("smoother", C.c_int), ("smoother_operator", C.c_int)]
+
+
+class TimeControlParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("time_end", C.c_double), ("adapt", C.c_int), ("max_cfl", C.c_double),
+                ("scaling", C.c_double), ("output_control", C.c_int), ("output_frequency", C.c_int),
+                ("output_time", C.c_double)]
+
+
+OUTPUT_CONTROL = {"iteration": 0, "time": 1}
 
 
 class RefinedMesh(C.Structure):
@@ -220,6 +231,14 @@ def load():
     L.gls_boundary_plan_create.argtypes = [vp, i64, C.c_int, pi32, pi32, d, d, d, d, d, C.c_int, C.POINTER(vp)]
     L.gls_boundary_plan_destroy.argtypes = [vp]
     L.gls_boundary_loads.argtypes = [vp, vp, vp, C.c_double, d, d, d]
+    L.gls_flow_diagnostics.argtypes = [vp, vp, C.c_double, d]
+    L.gls_time_control_create.argtypes = [C.POINTER(TimeControlParams), C.POINTER(vp)]
+    L.gls_time_control_destroy.argtypes = [vp]
+    L.gls_time_control_destroy.restype = None
+    L.gls_time_control_integrate.argtypes = [vp]
+    L.gls_time_control_set_cfl.argtypes = [vp, C.c_double]
+    L.gls_time_control_get.argtypes = [vp, C.POINTER(C.c_int), d, d, d]
+    L.gls_time_control_is_output_iteration.argtypes = [vp]
     _lib = L
     return L
 
@@ -261,6 +280,47 @@ def skip_newton_selftest(skip_iterations=1):
     out = np.zeros(2)
     check(load().gls_skip_newton_selftest(int(skip_iterations), _dp(out)), "gls_skip_newton_selftest")
     return out
+
+
+class TimeControl:
+    """The transient simulation control (gls_time_control_*): SimulationControlTransient and, with
+    output_control="time", SimulationControlTransientDynamicOutput of the reference. Host only."""
+
+    def __init__(self, dt, time_end, adapt=False, max_cfl=1.0, scaling=1.1, output_control="iteration",
+                 output_frequency=1, output_time=1.0):
+        if output_control not in OUTPUT_CONTROL:
+            raise GLSError("output control '%s' is unknown (iteration or time)" % output_control)
+        self.L = load()
+        prm = TimeControlParams(float(dt), float(time_end), int(bool(adapt)), float(max_cfl), float(scaling),
+                                OUTPUT_CONTROL[output_control], int(output_frequency), float(output_time))
+        self.h = C.c_void_p()
+        check(self.L.gls_time_control_create(C.byref(prm), C.byref(self.h)), "gls_time_control_create")
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.gls_time_control_destroy(self.h)
+            self.h = None
+
+    def integrate(self):
+        """Advance to the next iteration; False at the end of the simulation."""
+        return check(self.L.gls_time_control_integrate(self.h), "gls_time_control_integrate") == 1
+
+    def set_cfl(self, cfl):
+        check(self.L.gls_time_control_set_cfl(self.h, float(cfl)), "gls_time_control_set_cfl")
+
+    def is_output_iteration(self):
+        """Once per iteration: the time variant records the output time as a side effect."""
+        return check(self.L.gls_time_control_is_output_iteration(self.h), "gls_time_control_is_output_iteration") == 1
+
+    def _get(self):
+        it, t, dt, steps = C.c_int(), C.c_double(), C.c_double(), np.zeros(4)
+        check(self.L.gls_time_control_get(self.h, C.byref(it), C.byref(t), C.byref(dt), _dp(steps)), "gls_time_control_get")
+        return it.value, t.value, dt.value, steps
+
+    iteration = property(lambda self: self._get()[0])
+    time = property(lambda self: self._get()[1])
+    time_step = property(lambda self: self._get()[2])
+    time_steps = property(lambda self: self._get()[3])
 
 
 def hyper_cube(dim, n, k, kp=None, lo=-1.0, hi=1.0, periodic=()):
@@ -868,6 +928,14 @@ class GLSContext:
         check(self.L.gls_kelly_estimate_mapped(self.h, _ptr(sol), int(variable), len(f["ca"]), int(faces["nqf"]),
                                                p32(f["ca"]), p32(f["cb"]), _dp(f["xi"]), _dp(f["g"]), _dp(f["jxw"]),
                                                _dp(f["diam"]), _ptr(out)), "gls_kelly_estimate_mapped")
+        return out
+
+    def flow_diagnostics(self, sol, dt):
+        """(max CFL, int 1/2 |u|^2, int 1/2 |curl u|^2, volume) of a device solution vector in one pass over
+        the context's cells (gls_flow_diagnostics); the kinetic energy and enstrophy of the reference's
+        post-processing are the two integrals over the volume."""
+        out = np.zeros(4)
+        check(self.L.gls_flow_diagnostics(self.h, _ptr(sol), float(dt), _dp(out)), "gls_flow_diagnostics")
         return out
 
     def boundary_loads(self, faces, slots, n_slots, sol, viscosity, cor):
