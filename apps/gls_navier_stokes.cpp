@@ -1163,6 +1163,7 @@ struct Solver {
 
   void release() {
     release_boundary_plan();  // the plan belongs to the context destroyed below
+    release_output_plan();
     for (gls_ctx *g : mg_levels) gls_destroy(g);
     mg_levels.clear();
     for (gls_refined_mesh *R : mg_meshes) gls_octree_mesh_destroy(R);
@@ -2393,13 +2394,23 @@ struct Solver {
     }
     return cmax;
   }
+  // The point data of the piece on the device (gls_output_plan_create / gls_vtu_write_device): one launch over
+  // the cells from d_present, one download per array -- no download of the solution. The plan holds the patch
+  // geometry of the current mesh: released with the context (release(); setup / setup_refined / setup_general
+  // run after every refinement) and made at the first output after that, so a run without output pays nothing.
+  // --output-eval host keeps the host evaluation (gls_vtu_write); it also serves what the library has no kernel
+  // for (gls_output_plan_create answers GLS_EINVAL: 2D Q3, a subdivision past the kernel's) and --np, where rank 0
+  // writes the gathered solution.
+  gls_output_plan *oplan = nullptr;
+  bool oplan_refused = false;    // the library has no output kernel for this mesh: host evaluation
+  bool output_device = true;     // --output-eval
+  void release_output_plan() {
+    if (oplan) gls_output_plan_destroy(oplan);
+    oplan = nullptr;
+    oplan_refused = false;
+  }
   void write_output() {
     SectionTimer::Scope ts(timer, "output");
-    need_host();
-    if (rank != 0) return;  // --np: rank 0 writes the (gathered) solution
-    char tag[32];
-    std::snprintf(tag, sizeof(tag), ".%05d", step);
-    const std::string stem = P.output_name + tag, piece = stem + ".00000.vtu", master = stem + ".pvtu";
     gls_mesh_desc D;
     std::memset(&D, 0, sizeof(D));
     D.dim = m.dim;
@@ -2419,7 +2430,22 @@ struct Solver {
     }
     D.srf = P.srf ? 1 : 0;
     for (int i = 0; i < 3; ++i) D.omega[i] = P.omega[i];
-    ck(gls_vtu_write((P.output_path + piece).c_str(), &D, present.data(), P.subdivision, 0, 1), "gls_vtu_write");
+    bool on_device = output_device && world == 1 && !oplan_refused;
+    if (on_device && !oplan) {  // the library decides what it has a kernel for
+      const int rc = gls_output_plan_create(ctx, &D, P.subdivision, &oplan);
+      if (rc == GLS_EINVAL) oplan_refused = true, on_device = false;
+      else ck(rc, "gls_output_plan_create");
+    }
+    if (on_device) need_dev();
+    else need_host();
+    if (rank != 0) return;  // --np: rank 0 writes the (gathered) solution
+    char tag[32];
+    std::snprintf(tag, sizeof(tag), ".%05d", step);
+    const std::string stem = P.output_name + tag, piece = stem + ".00000.vtu", master = stem + ".pvtu";
+    if (on_device)
+      ck(gls_vtu_write_device(ctx, oplan, d_present, (P.output_path + piece).c_str(), 0, 1), "gls_vtu_write_device");
+    else
+      ck(gls_vtu_write((P.output_path + piece).c_str(), &D, present.data(), P.subdivision, 0, 1), "gls_vtu_write");
     const char *pc[1] = {piece.c_str()};
     ck(gls_pvtu_write((P.output_path + master).c_str(), m.dim, P.srf ? 1 : 0, 1, pc), "gls_pvtu_write");
     pvd.emplace_back(time, master);
@@ -3115,8 +3141,10 @@ int main(int argc, char **argv) {
   // multigrid on adapted meshes; hmg: that multigrid for every method and order), --precision N (error table digits),
   // --stats (solver iteration totals), --ilu-block-dofs N (block-Jacobi ILU subdomains of N DoFs,
   // 0 = one block), --ilu-order cm|multicolor (gls_ilu_set_options), --dump DIR (every iteration's
-  // final state for the pipeline tests).
+  // final state for the pipeline tests), --output-eval host|device (the VTU point data from the host vector or,
+  // the default, on the device from the device-resident solution).
   int dim = 0;
+  bool output_device = true;
   bool mg = true, stats = false;
   int64_t ilu_block = -1;
   int ilu_order = -1;
@@ -3147,6 +3175,11 @@ int main(int argc, char **argv) {
       if (!std::strcmp(o, "cm")) ilu_order = GLS_ILU_ORDER_CM;
       else if (!std::strcmp(o, "multicolor")) ilu_order = GLS_ILU_ORDER_MULTICOLOR;
       else die("--ilu-order %s: cm or multicolor", o);
+    }
+    else if (!std::strcmp(argv[i], "--output-eval") && i + 1 < argc) {
+      const char *o = argv[++i];
+      if (std::strcmp(o, "host") && std::strcmp(o, "device")) die("--output-eval %s: host or device", o);
+      output_device = !std::strcmp(o, "device");
     }
     else if (argv[i][0] != '-') file = argv[i];
     else die("unknown option %s", argv[i]);
@@ -3201,6 +3234,7 @@ int main(int argc, char **argv) {
   if (ilu_block >= 0) s.ilu_block_dofs = ilu_block;
   s.ilu_order = ilu_order;
   if (dump) s.dump_dir = dump;
+  s.output_device = output_device;
   s.run();
   if (np_ranks > 1) {
     g_comm.barrier("end");

@@ -678,6 +678,33 @@ int gls_boundary_loads(gls_ctx *ctx, gls_boundary_plan *plan, const double *sol,
  * out (HOST) is one download of 4 doubles. Kernels exist for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}
  * with QGauss(k+1); other degrees (2D Q3) are GLS_EINVAL. */
 int gls_flow_diagnostics(gls_ctx *ctx, const double *sol, double dt, double out[4]);
+/* The point data of a VTU piece evaluated on the DEVICE: what gls_vtu_write (below) derives on the host from a
+ * host vector, from a device vector (the context's layout, constrained DoFs holding their values) in one launch
+ * over all cells: for every cell and every patch point of DataOut::build_patches(mapping, subdivision)
+ * (navier_stokes_base.cc:1035-1064, post_processors.h:27-171), point P = cell * npp + p with p x-fastest over
+ * the (subdivision+1)^dim lattice,
+ *   points [P][3], velocity [P][3] (2D: z = 0), pressure [P], vorticity [P][3] (3D) or [P] (2D),
+ *   q_criterion [P] = 0.5 (sum_{p' <= p} |W|^2 - sum_{p' <= p} |S|^2) over the cell's points in patch order (the
+ *   reference's accumulators live outside its point loop, post_processors.h:84-115; the sums restart at every
+ *   cell), velocity_eulerian [P][3] = u + omega x x when the mesh has srf.
+ * gls_output_plan_create uploads the geometry the patch points need (box cells: cell_x0 / cell_h; mapped cells:
+ * cell_support, (map_degree+1)^dim dim doubles per cell) and the 1D tables at t / subdivision, and allocates the
+ * device field buffers once. mesh must be the description the context was created from (dim, k, kp, n_cells and
+ * map_degree are checked; srf / omega are the mesh's); rebuild the plan after an adaptation. Every layout of a
+ * context: brick, per-cell box, mapped, with hanging lines. gls_output_fields: the launch, then one download per
+ * array into HOST arrays (velocity_eulerian may be NULL without srf). gls_vtu_write_device: the same, then the
+ * file writer of gls_vtu_write -- equal arrays give equal bytes; the connectivity and subdomain arrays are
+ * gls_vtu_write's. The work is queued on the context's stream; no atomics, two calls on the same input are
+ * bitwise equal. With GLS_OUTPUT_SPLIT set in the environment gls_vtu_write_device prints its host seconds (launch
+ * and downloads, base64 encoding, the rest of the writer) on stderr. Kernels exist for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}, box and mapped (map_degree <= 3), with (subdivision+1)^dim <= 256
+ * (subdivision 1..15 in 2D, 1..5 in 3D); anything else (2D Q3) is GLS_EINVAL at gls_output_plan_create. */
+typedef struct gls_output_plan gls_output_plan;
+int gls_output_plan_create(gls_ctx *ctx, const gls_mesh_desc *mesh, int subdivision, gls_output_plan **plan);
+int gls_output_plan_destroy(gls_output_plan *plan);
+int gls_output_fields(gls_ctx *ctx, gls_output_plan *plan, const double *sol, double *points, double *velocity,
+                      double *pressure, double *vorticity, double *q_criterion, double *velocity_eulerian);
+int gls_vtu_write_device(gls_ctx *ctx, gls_output_plan *plan, const double *sol, const char *filename, int subdomain,
+                         int binary);
 /* GridRefinement::refine_and_coarsen_fixed_number, refinement part (navier_stokes_base.cc:654-661;
  * serial deal.II rule): flags[i] = 1 for the int(top_fraction * n_cells) largest criteria (every
  * cell >= the threshold value). Returns the number of flagged cells. HOST arrays. */

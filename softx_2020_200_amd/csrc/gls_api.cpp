@@ -3729,6 +3729,158 @@ int gls_flow_diagnostics(gls_ctx *c, const double *sol, double dt, double out[4]
   return GLS_OK;
 }
 
+// --------------------------------------------------------------------------------------------
+// VTU point data on the device (navier_stokes_base.cc:1035-1064, post_processors.h:27-171): the geometry of
+// one mesh and the 1D tables at the patch points uploaded once (plan), every output one launch over all
+// cells, one download per array and the file writer of gls_vtu_write
+// --------------------------------------------------------------------------------------------
+}  // extern "C"
+// gls_io.cpp: the 1D tables and the file writer shared with gls_vtu_write
+void gls_io_patch_tables(int degree, int ns, double *V, double *D);
+int gls_io_vtu_write_piece(const char *filename, int dim, int k, int64_t nc, int ns, int subdomain, int binary, int srf,
+                           const double *pts, const double *vel, const double *pre, const double *vort,
+                           const double *qcr, const double *eul, double *encode_seconds);
+extern "C" {
+
+struct gls_output_plan {
+  gls_ctx *ctx = nullptr;
+  int ns = 1, srf = 0;
+  double omega[3] = {0, 0, 0};
+  int64_t n_pts = 0;
+  DevBuf<double> x0h, support, tab;
+  DevBuf<double> pts, vel, pre, vort, qcr, eul;  // the device field buffers, allocated once
+  std::vector<double> h_pts, h_vel, h_pre, h_vort, h_qcr, h_eul;  // gls_vtu_write_device: the downloaded arrays
+};
+
+int gls_output_plan_create(gls_ctx *c, const gls_mesh_desc *m, int subdivision, gls_output_plan **out) {
+  GLS_TRY(check_ctx(c));
+  if (!m || !out) return set_err(GLS_EINVAL, "gls_output_plan_create: null argument");
+  if (m->dim != c->dim || m->k != c->k || m->kp != c->kp || m->n_cells != c->n_cells || m->map_degree != c->map_degree)
+    return set_err(GLS_EINVAL,
+                   "gls_output_plan_create: the mesh (%dD FE_Q(%d)-FE_Q(%d), %d cells, mapping degree %d) is not the "
+                   "context's (%dD FE_Q(%d)-FE_Q(%d), %d cells, mapping degree %d)",
+                   m->dim, m->k, m->kp, m->n_cells, m->map_degree, c->dim, c->k, c->kp, c->n_cells, c->map_degree);
+  if (!gls::output_fields_supported(c->dim, c->k, c->kp, c->map_degree, subdivision))
+    return set_err(GLS_EINVAL,
+                   "gls_output_plan_create: FE_Q(%d)-FE_Q(%d) in %dD with subdivision %d has no output kernel (velocity / "
+                   "pressure orders (1,1), (2,1), (2,2), 2D Q3 is not supported; (subdivision+1)^dim <= 256: subdivision "
+                   "1..15 in 2D, 1..5 in 3D)",
+                   c->k, c->kp, c->dim, subdivision);
+  const int dim = c->dim, md = c->map_degree, np1 = subdivision + 1;
+  if (md ? !m->cell_support : !m->cell_h)
+    return set_err(GLS_EINVAL, "gls_output_plan_create: the mesh has no %s", md ? "cell_support" : "cell_h");
+  std::unique_ptr<gls_output_plan> p(new gls_output_plan);
+  p->ctx = c;
+  p->ns = subdivision;
+  p->srf = m->srf ? 1 : 0;
+  for (int i = 0; i < 3; ++i) p->omega[i] = m->omega[i];
+  const size_t nc = (size_t)c->n_cells;
+  p->n_pts = (int64_t)nc * gls::ipow(np1, dim);
+  if (md) {
+    GLS_TRY(p->support.upload(m->cell_support, nc * (size_t)gls::ipow(md + 1, dim) * dim));
+  } else {
+    std::vector<double> x0h(nc * 2 * dim);
+    for (size_t cix = 0; cix < nc; ++cix)
+      for (int d = 0; d < dim; ++d) {
+        x0h[cix * 2 * dim + d] = m->cell_x0 ? m->cell_x0[cix * dim + d] : 0.0;
+        x0h[cix * 2 * dim + dim + d] = m->cell_h[cix * dim + d];
+      }
+    GLS_TRY(p->x0h.upload(x0h.data(), x0h.size()));
+  }
+  // Vv | Dv | Vp | Vm | Dm at t / subdivision
+  const int k1 = c->k + 1, kp1 = c->kp + 1, nm = md ? md + 1 : 0;
+  std::vector<double> tab((size_t)np1 * (2 * k1 + kp1 + 2 * nm));
+  gls_io_patch_tables(c->k, subdivision, tab.data(), tab.data() + np1 * k1);
+  gls_io_patch_tables(c->kp, subdivision, tab.data() + 2 * np1 * k1, nullptr);  // the pressure enters by value only
+  if (md) gls_io_patch_tables(md, subdivision, tab.data() + np1 * (2 * k1 + kp1), tab.data() + np1 * (2 * k1 + kp1 + nm));
+  GLS_TRY(p->tab.upload(tab.data(), tab.size()));
+  const size_t np = (size_t)p->n_pts;
+  GLS_TRY(p->pts.alloc(np * 3));
+  GLS_TRY(p->vel.alloc(np * 3));
+  GLS_TRY(p->pre.alloc(np));
+  GLS_TRY(p->vort.alloc(np * (dim == 3 ? 3 : 1)));
+  GLS_TRY(p->qcr.alloc(np));
+  if (p->srf) GLS_TRY(p->eul.alloc(np * 3));
+  *out = p.release();
+  return GLS_OK;
+}
+
+int gls_output_plan_destroy(gls_output_plan *plan) {
+  delete plan;
+  return GLS_OK;
+}
+
+namespace {
+// the launch and one download per array, all on the context's stream; the caller synchronizes
+int output_fields_queue(gls_ctx *c, gls_output_plan *p, const double *sol, double *pts, double *vel, double *pre,
+                        double *vort, double *qcr, double *eul) {
+  const size_t np = (size_t)p->n_pts;
+  if (np == 0) return GLS_OK;
+  if (!c->cell_pnodes.p && c->kp != c->k) return set_err(GLS_EINVAL, "output fields: the context has no cell_pnodes");
+  const int32_t *pn = c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;  // equal order: shared nodes
+  HIP_TRY(gls::launch_output_fields(c->dim, c->k, c->kp, c->map_degree, p->ns, c->cell_vnodes.p, pn, sol,
+                                    (int64_t)c->dim * c->n_vnodes, p->x0h.p, p->support.p, p->tab.p, c->n_cells, p->srf,
+                                    p->omega, p->pts.p, p->vel.p, p->pre.p, p->vort.p, p->qcr.p, p->eul.p, c->stream));
+  const struct { double *h; const double *d; size_t n; } a[6] = {
+      {pts, p->pts.p, np * 3}, {vel, p->vel.p, np * 3}, {pre, p->pre.p, np}, {vort, p->vort.p, np * (c->dim == 3 ? 3 : 1)},
+      {qcr, p->qcr.p, np},     {p->srf ? eul : nullptr, p->eul.p, np * 3}};
+  for (const auto &x : a)
+    if (x.h) HIP_TRY(hipMemcpyAsync(x.h, x.d, sizeof(double) * x.n, hipMemcpyDeviceToHost, c->stream));
+  return GLS_OK;
+}
+int output_plan_check(gls_ctx *c, gls_output_plan *p, const double *sol, const char *who) {
+  GLS_TRY(check_ctx(c));
+  if (!p || p->ctx != c) return set_err(GLS_EINVAL, "%s: the plan belongs to another context", who);
+  if (!sol) return set_err(GLS_EINVAL, "%s: null solution", who);
+  if (p->n_pts != (int64_t)c->n_cells * gls::ipow(p->ns + 1, c->dim))
+    return set_err(GLS_EINVAL, "%s: the context has changed since the plan was made", who);
+  return GLS_OK;
+}
+}  // namespace
+
+int gls_output_fields(gls_ctx *c, gls_output_plan *p, const double *sol, double *points, double *velocity,
+                      double *pressure, double *vorticity, double *q_criterion, double *velocity_eulerian) {
+  GLS_TRY(output_plan_check(c, p, sol, "gls_output_fields"));
+  if (!points || !velocity || !pressure || !vorticity || !q_criterion || (p->srf && !velocity_eulerian))
+    return set_err(GLS_EINVAL, "gls_output_fields: null output array");
+  GLS_TRY(output_fields_queue(c, p, sol, points, velocity, pressure, vorticity, q_criterion, velocity_eulerian));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return GLS_OK;
+}
+
+int gls_vtu_write_device(gls_ctx *c, gls_output_plan *p, const double *sol, const char *filename, int subdomain,
+                         int binary) {
+  GLS_TRY(output_plan_check(c, p, sol, "gls_vtu_write_device"));
+  if (!filename) return set_err(GLS_EINVAL, "gls_vtu_write_device: null file name");
+  // GLS_OUTPUT_SPLIT=1: host clocks to the synchronization, around the encoding and over the writer, on stderr
+  static const bool split = std::getenv("GLS_OUTPUT_SPLIT") != nullptr;
+  double enc = 0.0;
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t np = (size_t)p->n_pts;
+  if (p->h_pts.size() != np * 3) {  // once per plan
+    p->h_pts.resize(np * 3);
+    p->h_vel.resize(np * 3);
+    p->h_pre.resize(np);
+    p->h_vort.resize(np * (c->dim == 3 ? 3 : 1));
+    p->h_qcr.resize(np);
+    if (p->srf) p->h_eul.resize(np * 3);
+  }
+  GLS_TRY(output_fields_queue(c, p, sol, p->h_pts.data(), p->h_vel.data(), p->h_pre.data(), p->h_vort.data(),
+                              p->h_qcr.data(), p->h_eul.data()));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const auto t1 = std::chrono::steady_clock::now();
+  const int rc = gls_io_vtu_write_piece(filename, c->dim, c->k, c->n_cells, p->ns, subdomain, binary, p->srf,
+                                        p->h_pts.data(), p->h_vel.data(), p->h_pre.data(), p->h_vort.data(),
+                                        p->h_qcr.data(), p->srf ? p->h_eul.data() : nullptr, split ? &enc : nullptr);
+  if (split) {
+    const double dl = std::chrono::duration<double>(t1 - t0).count();
+    const double wr = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    std::fprintf(stderr, "gls_vtu_write_device: launch + downloads %.6f s, encode %.6f s, file write %.6f s\n", dl, enc,
+                 wr - enc);
+  }
+  return rc;
+}
+
 int gls_set_lattice(gls_ctx *c, int n1d, const int64_t *l2g) {
   GLS_TRY(check_ctx(c));
   if (c->dim != 3 || n1d < 2 || !l2g) return set_err(GLS_EINVAL, "gls_set_lattice: 3D, n1d >= 2, map required");

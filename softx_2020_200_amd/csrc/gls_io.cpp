@@ -10,7 +10,9 @@
 //     solutions_output.cc:14-59, post_processors.h:27-171): velocity, pressure, subdomain,
 //     vorticity, q_criterion [, velocity_eulerian for SRF], one patch per cell with
 //     `subdivision` intervals, Lagrange hexahedra / quadrilaterals when the velocity order > 1.
+#include <algorithm>
 #include <cctype>
+#include <chrono>
 #include <cerrno>
 #include <cmath>
 #include <cstdarg>
@@ -651,48 +653,136 @@ int vtk_lagrange_index(int dim, int n, int i, int j, int k) {
 int vtk_lagrange_index_2d_interior(int n, int i, int j) { return 4 * n + (i - 1) + (n - 1) * (j - 1); }
 
 const char kB64[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
-void base64(const unsigned char *p, size_t n, std::string &o) {
-  size_t i = 0;
-  for (; i + 2 < n; i += 3) {
-    const unsigned v = (unsigned)p[i] << 16 | (unsigned)p[i + 1] << 8 | p[i + 2];
-    o += kB64[v >> 18 & 63];
-    o += kB64[v >> 12 & 63];
-    o += kB64[v >> 6 & 63];
-    o += kB64[v & 63];
-  }
-  if (i < n) {
-    unsigned v = (unsigned)p[i] << 16;
-    if (i + 1 < n) v |= (unsigned)p[i + 1] << 8;
-    o += kB64[v >> 18 & 63];
-    o += kB64[v >> 12 & 63];
-    o += i + 1 < n ? kB64[v >> 6 & 63] : '=';
-    o += '=';
-  }
+inline char *b64_triple(char *o, unsigned b0, unsigned b1, unsigned b2) {
+  const unsigned v = b0 << 16 | b1 << 8 | b2;
+  o[0] = kB64[v >> 18 & 63];
+  o[1] = kB64[v >> 12 & 63];
+  o[2] = kB64[v >> 6 & 63];
+  o[3] = kB64[v & 63];
+  return o + 4;
 }
+// base64 of the UInt64 byte count nb followed by the nb bytes at p, as one stream, written straight from the
+// array to o (4 * ceil((8 + nb) / 3) characters): no copy of the array behind its header. Returns the end.
+char *base64_block(uint64_t nb, const unsigned char *p, char *o) {
+  unsigned char h[8];
+  std::memcpy(h, &nb, 8);
+  o = b64_triple(o, h[0], h[1], h[2]);
+  o = b64_triple(o, h[3], h[4], h[5]);
+  if (nb == 0) {  // two bytes left over
+    o = b64_triple(o, h[6], h[7], 0);
+    o[-1] = '=';
+    return o;
+  }
+  o = b64_triple(o, h[6], h[7], p[0]);
+  uint64_t i = 1;
+  for (; i + 2 < nb; i += 3) o = b64_triple(o, p[i], p[i + 1], p[i + 2]);
+  if (i < nb) {
+    const bool two = i + 1 < nb;
+    o = b64_triple(o, p[i], two ? p[i + 1] : 0, 0);
+    o[-1] = '=';
+    if (!two) o[-2] = '=';
+  }
+  return o;
+}
+// buf: the file's one encode buffer, sized once for its largest array (vtu_encode_chars)
+size_t vtu_encode_chars(size_t n_bytes) { return (sizeof(uint64_t) + n_bytes + 2) / 3 * 4 + 1; }
+// enc (null: no clock is read): the seconds spent encoding are added to it
 template <typename T>
-void write_array(std::ostream &f, const char *type, const char *name, int ncomp, const std::vector<T> &a, bool binary) {
+void write_array(std::ostream &f, const char *type, const char *name, int ncomp, const T *a, size_t n, bool binary,
+                 std::vector<char> &buf, double *enc) {
   f << "    <DataArray type=\"" << type << "\"";
   if (name) f << " Name=\"" << name << "\"";
   if (ncomp > 1) f << " NumberOfComponents=\"" << ncomp << "\"";
   f << " format=\"" << (binary ? "binary" : "ascii") << "\">\n";
   if (binary) {
-    const uint64_t nb = a.size() * sizeof(T);
-    std::vector<unsigned char> buf(sizeof(uint64_t) + nb);
-    std::memcpy(buf.data(), &nb, sizeof(uint64_t));
-    if (nb) std::memcpy(buf.data() + sizeof(uint64_t), a.data(), nb);
-    std::string s;
-    s.reserve(buf.size() * 4 / 3 + 8);
-    base64(buf.data(), buf.size(), s);
-    f << s << "\n";
+    const uint64_t nb = n * sizeof(T);
+    if (buf.size() < vtu_encode_chars(nb)) buf.resize(vtu_encode_chars(nb));
+    const auto t0 = enc ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+    char *e = base64_block(nb, reinterpret_cast<const unsigned char *>(a), buf.data());
+    if (enc) *enc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *e++ = '\n';
+    f.write(buf.data(), e - buf.data());
   } else {
     f.precision(17);
-    for (size_t i = 0; i < a.size(); ++i) f << a[i] << ((i + 1) % 12 ? " " : "\n");
+    for (size_t i = 0; i < n; ++i) f << a[i] << ((i + 1) % 12 ? " " : "\n");
     f << "\n";
   }
   f << "    </DataArray>\n";
 }
 
 }  // namespace
+
+// The file of one piece from its point data (gls_vtu_write and gls_vtu_write_device): connectivity, the subdomain
+// array and the XML. pts / vel / eul [P][3], pre / qcr [P], vort [P][3] (3D) or [P] (2D), P = n_cells * (ns+1)^dim.
+// encode_seconds (may be null): the seconds of the base64 encoding inside the call.
+int gls_io_vtu_write_piece(const char *filename, int dim, int k, int64_t nc, int ns, int subdomain, int binary, int srf,
+                           const double *pts, const double *vel, const double *pre, const double *vort,
+                           const double *qcr, const double *eul, double *encode_seconds) {
+  double *const enc = encode_seconds;
+  if (enc) *enc = 0.0;
+  const int np1 = ns + 1, npp = dim == 3 ? np1 * np1 * np1 : np1 * np1;
+  const bool high = k > 1;  // navier_stokes_base.cc:1027-1029 write_higher_order_cells
+  const int64_t npts = nc * npp;
+  const std::vector<double> sub((size_t)npts, (double)subdomain);
+  std::vector<int64_t> conn, offs;
+  std::vector<uint8_t> types;
+  if (high) {  // one Lagrange cell of order ns per patch
+    std::vector<int> perm(npp);
+    for (int p = 0; p < npp; ++p) {
+      const int i = p % np1, j = (p / np1) % np1, kk = dim == 3 ? p / (np1 * np1) : 0;
+      int idx;
+      if (dim == 2 && i > 0 && i < ns && j > 0 && j < ns) idx = vtk_lagrange_index_2d_interior(ns, i, j);
+      else idx = vtk_lagrange_index(dim, ns, i, j, kk);
+      perm[idx] = p;
+    }
+    conn.reserve((size_t)(nc * npp));
+    for (int64_t c = 0; c < nc; ++c) {
+      for (int q = 0; q < npp; ++q) conn.push_back(c * npp + perm[q]);
+      offs.push_back((c + 1) * npp);
+      types.push_back(dim == 3 ? 72 : 70);  // VTK_LAGRANGE_HEXAHEDRON / _QUADRILATERAL
+    }
+  } else {  // ns^dim linear cells per patch
+    const int nsub = dim == 3 ? ns * ns * ns : ns * ns, nv = dim == 3 ? 8 : 4;
+    const int corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
+    for (int64_t c = 0; c < nc; ++c)
+      for (int s = 0; s < nsub; ++s) {
+        const int s0 = s % ns, s1 = (s / ns) % ns, s2 = dim == 3 ? s / (ns * ns) : 0;
+        for (int v = 0; v < nv; ++v)
+          conn.push_back(c * npp + (s0 + corner[v][0]) + np1 * ((s1 + corner[v][1]) + np1 * (s2 + corner[v][2])));
+        offs.push_back((int64_t)conn.size());
+        types.push_back(dim == 3 ? 12 : 9);  // VTK_HEXAHEDRON / VTK_QUAD
+      }
+  }
+  std::ofstream f(filename, std::ios::binary);
+  if (!f) return gls_io_set_error(GLS_EIO, "cannot write %s", filename);
+  std::vector<char> buf;  // the one encode buffer: the largest array is the connectivity or a 3-component field
+  if (binary) buf.resize(vtu_encode_chars(std::max(conn.size() * sizeof(int64_t), (size_t)npts * 3 * sizeof(double))));
+  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\""
+       " header_type=\"UInt64\">\n<UnstructuredGrid>\n<Piece NumberOfPoints=\""
+    << npts << "\" NumberOfCells=\"" << types.size() << "\">\n  <Points>\n";
+  write_array(f, "Float64", nullptr, 3, pts, (size_t)npts * 3, binary, buf, enc);
+  f << "  </Points>\n  <Cells>\n";
+  write_array(f, "Int64", "connectivity", 1, conn.data(), conn.size(), binary, buf, enc);
+  write_array(f, "Int64", "offsets", 1, offs.data(), offs.size(), binary, buf, enc);
+  write_array(f, "UInt8", "types", 1, types.data(), types.size(), binary, buf, enc);
+  f << "  </Cells>\n  <PointData Scalars=\"pressure\" Vectors=\"velocity\">\n";
+  write_array(f, "Float64", "velocity", 3, vel, (size_t)npts * 3, binary, buf, enc);
+  write_array(f, "Float64", "pressure", 1, pre, (size_t)npts, binary, buf, enc);
+  write_array(f, "Float64", "subdomain", 1, sub.data(), sub.size(), binary, buf, enc);
+  write_array(f, "Float64", "vorticity", dim == 3 ? 3 : 1, vort, (size_t)npts * (dim == 3 ? 3 : 1), binary, buf, enc);
+  write_array(f, "Float64", "q_criterion", 1, qcr, (size_t)npts, binary, buf, enc);
+  if (srf) write_array(f, "Float64", "velocity_eulerian", 3, eul, (size_t)npts * 3, binary, buf, enc);
+  f << "  </PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
+  return f.good() ? GLS_OK : gls_io_set_error(GLS_EIO, "write error on %s", filename);
+}
+
+// 1D Lagrange basis of FE_Q(degree) and its derivative at t / ns, t = 0..ns: V, D [ns+1][degree+1] (the tables of
+// gls_vtu_write, for the device plan); D may be null
+void gls_io_patch_tables(int degree, int ns, double *V, double *D) {
+  const std::vector<double> xn = lobatto_nodes(degree);
+  std::vector<double> d((size_t)degree + 1);
+  for (int t = 0; t <= ns; ++t) lagrange(xn, (double)t / ns, V + t * (degree + 1), D ? D + t * (degree + 1) : d.data());
+}
 
 extern "C" {
 
@@ -712,7 +802,6 @@ int gls_vtu_write(const char *filename, const gls_mesh_desc *m, const double *so
   const int nk = k + 1, nkp = kp + 1, nvl = dim == 3 ? nk * nk * nk : nk * nk;
   const int npl = dim == 3 ? nkp * nkp * nkp : nkp * nkp;
   const int np1 = ns + 1, npp = dim == 3 ? np1 * np1 * np1 : np1 * np1;
-  const bool high = k > 1;  // navier_stokes_base.cc:1027-1029 write_higher_order_cells
   const int64_t nc = m->n_cells;
   const std::vector<double> xv = lobatto_nodes(k), xp = lobatto_nodes(kp);
   // 1D tables at the patch points
@@ -723,7 +812,7 @@ int gls_vtu_write(const char *filename, const gls_mesh_desc *m, const double *so
   }
   const int64_t npts = nc * npp;
   std::vector<double> pts((size_t)npts * 3), vel((size_t)npts * 3), pre((size_t)npts), vort((size_t)npts * (dim == 3 ? 3 : 1)),
-      qcr((size_t)npts), sub((size_t)npts, (double)subdomain), eul;
+      qcr((size_t)npts), eul;
   if (m->srf) eul.resize((size_t)npts * 3);
   const int64_t nvdof = (int64_t)dim * m->n_vnodes;
   // mapped cells: MappingQ(md) through the support points (build_patches(mapping, ...),
@@ -829,55 +918,8 @@ int gls_vtu_write(const char *filename, const gls_mesh_desc *m, const double *so
       }
     }
   }
-  // connectivity
-  std::vector<int64_t> conn, offs;
-  std::vector<uint8_t> types;
-  if (high) {  // one Lagrange cell of order ns per patch
-    std::vector<int> perm(npp);
-    for (int p = 0; p < npp; ++p) {
-      const int i = p % np1, j = (p / np1) % np1, kk = dim == 3 ? p / (np1 * np1) : 0;
-      int idx;
-      if (dim == 2 && i > 0 && i < ns && j > 0 && j < ns) idx = vtk_lagrange_index_2d_interior(ns, i, j);
-      else idx = vtk_lagrange_index(dim, ns, i, j, kk);
-      perm[idx] = p;
-    }
-    conn.reserve((size_t)(nc * npp));
-    for (int64_t c = 0; c < nc; ++c) {
-      for (int q = 0; q < npp; ++q) conn.push_back(c * npp + perm[q]);
-      offs.push_back((c + 1) * npp);
-      types.push_back(dim == 3 ? 72 : 70);  // VTK_LAGRANGE_HEXAHEDRON / _QUADRILATERAL
-    }
-  } else {  // ns^dim linear cells per patch
-    const int nsub = dim == 3 ? ns * ns * ns : ns * ns, nv = dim == 3 ? 8 : 4;
-    const int corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
-    for (int64_t c = 0; c < nc; ++c)
-      for (int s = 0; s < nsub; ++s) {
-        const int s0 = s % ns, s1 = (s / ns) % ns, s2 = dim == 3 ? s / (ns * ns) : 0;
-        for (int v = 0; v < nv; ++v)
-          conn.push_back(c * npp + (s0 + corner[v][0]) + np1 * ((s1 + corner[v][1]) + np1 * (s2 + corner[v][2])));
-        offs.push_back((int64_t)conn.size());
-        types.push_back(dim == 3 ? 12 : 9);  // VTK_HEXAHEDRON / VTK_QUAD
-      }
-  }
-  std::ofstream f(filename, std::ios::binary);
-  if (!f) return gls_io_set_error(GLS_EIO, "cannot write %s", filename);
-  f << "<?xml version=\"1.0\"?>\n<VTKFile type=\"UnstructuredGrid\" version=\"1.0\" byte_order=\"LittleEndian\""
-       " header_type=\"UInt64\">\n<UnstructuredGrid>\n<Piece NumberOfPoints=\""
-    << npts << "\" NumberOfCells=\"" << types.size() << "\">\n  <Points>\n";
-  write_array(f, "Float64", nullptr, 3, pts, binary);
-  f << "  </Points>\n  <Cells>\n";
-  write_array(f, "Int64", "connectivity", 1, conn, binary);
-  write_array(f, "Int64", "offsets", 1, offs, binary);
-  write_array(f, "UInt8", "types", 1, types, binary);
-  f << "  </Cells>\n  <PointData Scalars=\"pressure\" Vectors=\"velocity\">\n";
-  write_array(f, "Float64", "velocity", 3, vel, binary);
-  write_array(f, "Float64", "pressure", 1, pre, binary);
-  write_array(f, "Float64", "subdomain", 1, sub, binary);
-  write_array(f, "Float64", "vorticity", dim == 3 ? 3 : 1, vort, binary);
-  write_array(f, "Float64", "q_criterion", 1, qcr, binary);
-  if (m->srf) write_array(f, "Float64", "velocity_eulerian", 3, eul, binary);
-  f << "  </PointData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n";
-  return f.good() ? GLS_OK : gls_io_set_error(GLS_EIO, "write error on %s", filename);
+  return gls_io_vtu_write_piece(filename, dim, k, nc, ns, subdomain, binary, m->srf, pts.data(), vel.data(), pre.data(),
+                                vort.data(), qcr.data(), m->srf ? eul.data() : nullptr, nullptr);
 }
 
 // parallel master record (write_pvtu_record) over the ranks' pieces

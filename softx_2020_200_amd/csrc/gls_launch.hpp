@@ -218,6 +218,21 @@ hipError_t launch_flow_diagnostics(int dim, int k, const int32_t *cell_vnodes, c
                                    const double *meas, const double *tab, const double *sol, int64_t n_cells, double dt,
                                    double *partial, double *out, hipStream_t s);
 
+// ---- VTU point data (gls_output.hip): for every cell and every patch point of build_patches(mapping,
+// subdivision) the position, velocity, pressure, vorticity, running-sum q_criterion and (srf) velocity_eulerian,
+// in the VTU layout: point P = cell * npp + p, p x-fastest over the (subdivision+1)^dim lattice; pts / vel / eul
+// [P][3], pre / qcr [P], vort [P][3] (3D) or [P] (2D). One lane per patch point, sum-factorized through LDS.
+// x0h [n_cells][2 dim] = x0 | h (box cells, map_degree 0) or support [n_cells][(map_degree+1)^dim][dim]; tab =
+// Vv [np1][k+1] | Dv | Vp [np1][kp+1] | Vm [np1][map_degree+1] | Dm (the last two for mapped cells only): the 1D
+// bases and derivatives at t / subdivision. Instantiated for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}, box
+// and mapped (map_degree <= 3); (subdivision+1)^dim <= 256.
+bool output_fields_supported(int dim, int k, int kp, int map_degree, int subdivision);
+hipError_t launch_output_fields(int dim, int k, int kp, int map_degree, int subdivision, const int32_t *cell_vnodes,
+                                const int32_t *cell_pnodes, const double *sol, int64_t pbase, const double *x0h,
+                                const double *support, const double *tab, int64_t n_cells, int srf, const double *omega,
+                                double *pts, double *vel, double *pre, double *vort, double *qcr, double *eul,
+                                hipStream_t s);
+
 // ---- geometric multigrid (gls_mg_kernels.hip): nested Qk node lattices (boxes), k <= 2
 hipError_t mg_inject(const double *fine, double *coarse, const int nf[3], const int nc[3], hipStream_t s);
 // one-pass 3D transfer with per-axis tap tables [n_out][5] (index, weight) and tap counts [n_out]

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from .native import GLSError, MeshDesc, check, load
+from .native import GLSError, MeshDesc, check, load, mesh_desc
 
 GLS_ENOTFOUND = -7
 
@@ -95,26 +95,13 @@ class Expr:
 
 
 def write_vtu(filename, mesh, solution, subdivision=1, subdomain=0, binary=True, srf=False, omega=(0., 0., 0.)):
-    """One VTU piece of a host solution vector on a mesh dict (softx_2020_200_amd.hyper_cube layout)."""
+    """One VTU piece of a host solution vector on a mesh dict (softx_2020_200_amd.hyper_cube layout; mapped meshes
+    carry map_degree and cell_support) or a problem object with the same attributes."""
     L = _bind()
-    dim, k, kp = mesh["dim"], mesh["k"], mesh["kp"]
-    cv = np.ascontiguousarray(mesh["cell_vnodes"], dtype=np.int32)
-    cpn = mesh.get("cell_pnodes") if kp != k else None
-    cpn = np.ascontiguousarray(cpn, dtype=np.int32) if cpn is not None else None
-    x0 = np.ascontiguousarray(mesh["cell_x0"], dtype=np.float64)
-    h = np.ascontiguousarray(mesh["cell_h"], dtype=np.float64)
+    md, _keep = mesh_desc(mesh, srf, omega)
     sol = np.ascontiguousarray(solution, dtype=np.float64)
-    if sol.size != dim * mesh["n_vnodes"] + mesh["n_pnodes"]:
+    if sol.size != md.dim * md.n_vnodes + md.n_pnodes:
         raise GLSError("solution length %d does not match the mesh" % sol.size)
-    md = MeshDesc()
-    md.dim, md.k, md.kp, md.nq1d = dim, k, kp, 0
-    md.n_cells, md.n_vnodes, md.n_pnodes = cv.shape[0], mesh["n_vnodes"], mesh["n_pnodes"]
-    md.cell_vnodes = cv.ctypes.data_as(C.POINTER(C.c_int32))
-    md.cell_pnodes = cpn.ctypes.data_as(C.POINTER(C.c_int32)) if cpn is not None else None
-    md.cell_x0 = x0.ctypes.data_as(C.POINTER(C.c_double))
-    md.cell_h = h.ctypes.data_as(C.POINTER(C.c_double))
-    md.srf = 1 if srf else 0
-    md.omega = (C.c_double * 3)(*omega)
     check(L.gls_vtu_write(filename.encode(), C.byref(md), sol.ctypes.data_as(C.POINTER(C.c_double)), int(subdivision),
                           int(subdomain), 1 if binary else 0), "gls_vtu_write")
 

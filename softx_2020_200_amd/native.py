@@ -49,6 +49,7 @@ EXPORTS = [
     "gls_fe_space_boundary_faces", "gls_boundary_plan_create", "gls_boundary_plan_destroy", "gls_boundary_loads",
     "gls_flow_diagnostics", "gls_time_control_create", "gls_time_control_destroy", "gls_time_control_integrate",
     "gls_time_control_set_cfl", "gls_time_control_get", "gls_time_control_is_output_iteration",
+    "gls_output_plan_create", "gls_output_plan_destroy", "gls_output_fields", "gls_vtu_write_device",
 ]
 
 
@@ -232,6 +233,10 @@ def load():
     L.gls_boundary_plan_destroy.argtypes = [vp]
     L.gls_boundary_loads.argtypes = [vp, vp, vp, C.c_double, d, d, d]
     L.gls_flow_diagnostics.argtypes = [vp, vp, C.c_double, d]
+    L.gls_output_plan_create.argtypes = [vp, C.POINTER(MeshDesc), C.c_int, C.POINTER(vp)]
+    L.gls_output_plan_destroy.argtypes = [vp]
+    L.gls_output_fields.argtypes = [vp, vp, vp, d, d, d, d, d, d]
+    L.gls_vtu_write_device.argtypes = [vp, vp, vp, C.c_char_p, C.c_int, C.c_int]
     L.gls_time_control_create.argtypes = [C.POINTER(TimeControlParams), C.POINTER(vp)]
     L.gls_time_control_destroy.argtypes = [vp]
     L.gls_time_control_destroy.restype = None
@@ -252,6 +257,39 @@ def check(rc, what=""):
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else C.POINTER(C.c_double)()
+
+
+def mesh_desc(mesh, srf=False, omega=(0.0, 0.0, 0.0)):
+    """(MeshDesc, the arrays it points into) of a mesh dict (hyper_cube's keys; mapped meshes carry map_degree and
+    cell_support) or of an object with those attributes (the oracle's problems): what the output writers read."""
+    get = mesh.get if isinstance(mesh, dict) else lambda key, default=None: getattr(mesh, key, default)
+    dim, k, kp = int(get("dim")), int(get("k")), int(get("kp"))
+    keep = []
+
+    def arr(a, dt):
+        if a is None:
+            return None
+        keep.append(np.ascontiguousarray(a, dtype=dt))
+        return keep[-1]
+
+    cv = arr(get("cell_vnodes"), np.int32)
+    cp = arr(get("cell_pnodes"), np.int32) if kp != k else None
+    md = int(get("map_degree") or 0) if get("cell_support") is not None else 0
+    D = MeshDesc()
+    D.dim, D.k, D.kp, D.nq1d = dim, k, kp, 0
+    D.n_cells, D.n_vnodes, D.n_pnodes = cv.shape[0], int(get("n_vnodes")), int(get("n_pnodes"))
+    D.cell_vnodes = cv.ctypes.data_as(C.POINTER(C.c_int32))
+    D.cell_pnodes = cp.ctypes.data_as(C.POINTER(C.c_int32)) if cp is not None else C.POINTER(C.c_int32)()
+    if md:
+        D.map_degree = md
+        D.cell_support = _dp(arr(get("cell_support"), np.float64))
+    else:
+        D.cell_x0 = _dp(arr(get("cell_x0"), np.float64))
+        D.cell_h = _dp(arr(get("cell_h"), np.float64))
+    D.srf = 1 if srf else 0
+    for i in range(3):
+        D.omega[i] = float(omega[i])
+    return D, keep
 
 
 # ---------------------------------------------------------------------------------------------
@@ -964,6 +1002,13 @@ class GLSContext:
             self.L.gls_boundary_plan_destroy(plan)
         return force, torque
 
+    def output_plan(self, mesh, subdivision=1, srf=False, omega=(0.0, 0.0, 0.0)):
+        """The device evaluation of a VTU piece's point data on this context's cells (gls_output_plan_create):
+        mesh is the mesh the context was created from (a dict with hyper_cube's keys, or a problem object;
+        mapped meshes carry map_degree and cell_support), subdivision the patch subdivision. Make a new plan
+        after an adaptation."""
+        return OutputPlan(self, mesh, subdivision, srf, omega)
+
     def mg_transfer(self, level, direction, v, out):
         """Restrict (direction 0: level -> level+1) or prolongate (1: level+1 -> level) a device vector."""
         check(self.L.gls_mg_transfer(self.h, int(level), int(direction), _ptr(v), _ptr(out)), "gls_mg_transfer")
@@ -1050,6 +1095,48 @@ class GLSContext:
 # unstructured / curved meshes (host side, gls_umesh_* / gls_fe_space_*)
 # ---------------------------------------------------------------------------------------------
 MANIFOLD_TYPES = {"flat": 0, "spherical": 1, "cylindrical": 2}
+
+
+class OutputPlan:
+    """One gls_output_plan: the patch-point geometry and tables of one mesh on the device, and the field buffers."""
+
+    def __init__(self, ctx, mesh, subdivision, srf=False, omega=(0.0, 0.0, 0.0)):
+        self.ctx, self.L = ctx, ctx.L
+        D, keep = mesh_desc(mesh, srf, omega)
+        self.dim, self.srf = D.dim, bool(srf)
+        self.n_points = D.n_cells * (int(subdivision) + 1) ** D.dim
+        h = C.c_void_p()
+        check(self.L.gls_output_plan_create(ctx.h, C.byref(D), int(subdivision), C.byref(h)), "gls_output_plan_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gls_output_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def fields(self, sol):
+        """dict of numpy arrays of a device solution vector: points, velocity [P][3], pressure, q_criterion [P],
+        vorticity [P][3] (3D) or [P] (2D), and velocity_eulerian [P][3] with srf (gls_output_fields)"""
+        n = self.n_points
+        out = dict(points=np.zeros((n, 3)), velocity=np.zeros((n, 3)), pressure=np.zeros(n),
+                   vorticity=np.zeros((n, 3)) if self.dim == 3 else np.zeros(n), q_criterion=np.zeros(n))
+        if self.srf:
+            out["velocity_eulerian"] = np.zeros((n, 3))
+        check(self.L.gls_output_fields(self.ctx.h, self.h, _ptr(sol), _dp(out["points"]), _dp(out["velocity"]),
+                                       _dp(out["pressure"]), _dp(out["vorticity"]), _dp(out["q_criterion"]),
+                                       _dp(out.get("velocity_eulerian"))), "gls_output_fields")
+        return out
+
+    def write_vtu(self, filename, sol, subdomain=0, binary=True):
+        """one VTU piece of a device solution vector: the fields on the device, gls_vtu_write's file writer"""
+        check(self.L.gls_vtu_write_device(self.ctx.h, self.h, _ptr(sol), str(filename).encode(), int(subdomain),
+                                          1 if binary else 0), "gls_vtu_write_device")
 
 
 class UMesh:
