@@ -287,6 +287,15 @@ int gls_mg_transfer(gls_ctx *ctx, int level, int direction, const double *in, do
  * GLS_MG_FUSE_TRANSFER=0 / GLS_MG_NO_FUSE in the environment, by the separate residual, transfer and
  * zeroing launches. *fused (may be NULL) reports which of the two ran. */
 int gls_mg_residual_restrict(gls_ctx *ctx, int level, const double *x, const double *b, double *bc, int *fused);
+/* Debug / test entry: the V-cycle's prolongation and first post-sweep on level `level` at the current state,
+ * x <- S(x + P xc) with one damped-Jacobi (or ILU) sweep S of damping omega >= 0 for the right-hand side b (DEVICE
+ * pointers; x, b: level `level` vectors, x updated in place; xc: level `level`+1). Where the level pair is eligible
+ * (one rank, FP32 smoothing with the fused Jacobi sweep on the hyper_cube's Q2 bricks, nested lattice levels,
+ * at least one post-sweep) the coarse correction is interpolated inside the sweep's J.v and slab-sum launches;
+ * else, or with GLS_MG_FUSE_PROLONG=0 / GLS_MG_NO_FUSE in the environment, by the separate transfer launches
+ * before the sweep. *fused (may be NULL) reports which of the two ran. */
+int gls_mg_prolong_smooth(gls_ctx *ctx, int level, const double *xc, double *x, const double *b, double omega,
+                          int *fused);
 /* Lattice embedding of a (rank-local) mesh: its velocity nodes are a subset of the global n1d^3
  * Qk node lattice of hyper_cube in canonical numbering (global id = x + n1d*(y + n1d*z)), local
  * node i being global node local_to_global[i] (host array, n_vnodes entries). The local nodes

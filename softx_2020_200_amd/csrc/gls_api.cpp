@@ -1148,11 +1148,12 @@ int ensure_qdata(gls_ctx *c) {
 
 // the slab node sums with an FP32 slab and / or the fused damped-Jacobi sweep / residual form
 hipError_t slab_sum_ex(gls_ctx *g, const double *slab, const float *slabf, double *y, const uint8_t *vmask,
-                       const double *jb, const double *jd, double omega, const double *rb, double *x0 = nullptr) {
+                       const double *jb, const double *jd, double omega, const double *rb, double *x0 = nullptr,
+                       const double *xs = nullptr) {
   if (g->cube_nb1 > 0)
     return gls::brick_slab_sum_cube(g->k, g->cube_nb1, slab, slabf, g->n_vnodes, y, vmask, jb, jd, omega, g->stream, rb,
-                                    x0);
-  if (x0) return hipErrorInvalidValue;
+                                    x0, xs);
+  if (x0 || xs) return hipErrorInvalidValue;
   return gls::brick_slab_sum_ex(slab, slabf, g->sum_nodes.p, g->sum_off.p, g->sum_slots.p, (int64_t)g->sum_nodes.n,
                                 g->n_vnodes, y, vmask, jb, jd, omega, g->stream, rb);
 }
@@ -1976,7 +1977,8 @@ bool slab_f32() { return std::getenv("GLS_SLAB_F64") == nullptr; }
 // stored to v by the J.v (brick-interior nodes) and the slab sum (surface nodes). Opt-in
 // (GLS_MG_FIRST_FUSE=1): bitwise the separate update, but measured slower at Q2 128^3 (99.5 vs 96.0 ms per
 // Newton step, profiles/r04_ab_env_switches.txt: the gather's two extra FP64 loads and FP64 divisions per
-// node cost the J.v more than the update pass it saves)
+// node cost the J.v more than the update pass it saves; with the restriction inside that J.v still no win,
+// 79.5-79.9 vs 78.6-79.5 ms, profiles/fused_prolongation_ab.txt)
 bool first_sweep_fusable(gls_ctx *g) {
   const char *e = std::getenv("GLS_MG_FIRST_FUSE");
   return e && std::atoi(e) != 0 && g->smooth_f32 && g->use_brick && g->use_qdata && !g->use_colors && !g->dist.on &&
@@ -2035,6 +2037,9 @@ int smoother_apply(gls_ctx *g, const double *v, double *y, const double *rb = nu
 // one damped-Jacobi sweep x <- x + omega D^-1 (b - A x) with the smoother's operator A (constrained
 // rows D_c x). Single rank on the brick path: fused into the J.v (brick-interior nodes) and the slab
 // sum (brick-surface nodes), so A x is never stored; otherwise smoother_apply + mg_jacobi_update.
+// pxc != nullptr (only where mg_fused_prolong_ok): the sweep starts from x + P pxc, the coarse correction of the
+// next-coarser nested level interpolated in the J.v's gather; y (scratch) carries x + P pxc of the brick-surface
+// nodes from the J.v to the slab sum.
 }  // namespace
 static int ensure_ilu(gls_ctx *c);
 static int ilu_probe(gls_ctx *c);
@@ -2049,11 +2054,14 @@ int ilu_sweep(gls_ctx *g, double *x, const double *b, double *y, double *z) {
   HIP_TRY(gls::vec_axpy(x, 1.0, z, g->n_dofs, g->stream));
   return GLS_OK;
 }
-int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double omega, double *z = nullptr) {
-  if (z && g->ilu.on && !g->ilu.probe_only) return ilu_sweep(g, x, b, y, z);
+int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double omega, double *z = nullptr,
+                   const double *pxc = nullptr) {
   const bool nofuse = std::getenv("GLS_MG_NO_FUSE") != nullptr;
   const bool brick = g->use_brick && g->use_qdata && (g->use_colors || brick_slab(g)) && !g->dist.on &&
                      !g->hang.on && gls::brick_fused_jacobi_supported(g->k);
+  if (pxc && ((z && g->ilu.on && !g->ilu.probe_only) || nofuse || !brick || !g->smooth_f32 || g->use_colors || g->cube_nb1 <= 0))
+    return set_err(GLS_EINVAL, "fused prolongation not applicable");
+  if (z && g->ilu.on && !g->ilu.probe_only) return ilu_sweep(g, x, b, y, z);
   if (nofuse || !brick) {
     GLS_TRY(smoother_apply(g, x, y));
     HIP_TRY(gls::mg_jacobi_update(x, b, y, g->diag.p, omega, g->n_dofs, 0, g->stream));
@@ -2080,8 +2088,12 @@ int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double ome
     P.qdf = g->qdata32.p;
     P.oseen = g->smooth_oseen ? 1 : 0;
     P.slabf = P.slab && slab_f32() ? reinterpret_cast<float *>(P.slab) : nullptr;
+    P.pxc = pxc;
+    P.pxp = pxc ? y : nullptr;
+    P.cube_nb1 = g->cube_nb1;
     TimedLaunch t(g, 4);
-    HIP_TRY(gls::launch_brick_jv_f32(g->k, P, g->tables, g->stream));
+    HIP_TRY(pxc ? gls::launch_pencil_jv_prolong(P, g->tables, g->stream)
+                : gls::launch_brick_jv_f32(g->k, P, g->tables, g->stream));
   } else {
     P.qd = g->qdata.p;
     TimedLaunch t(g, 1);
@@ -2089,7 +2101,7 @@ int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double ome
   }
   if (g->use_colors) return GLS_OK;
   TimedLaunch t(g, 5);
-  HIP_TRY(slab_sum_ex(g, P.slab, P.slabf, x, g->vmask.p, b, g->diag.p, omega, nullptr));
+  HIP_TRY(slab_sum_ex(g, P.slab, P.slabf, x, g->vmask.p, b, g->diag.p, omega, nullptr, nullptr, pxc ? y : nullptr));
   return GLS_OK;
 }
 }  // namespace
@@ -2867,6 +2879,29 @@ int mg_residual_restrict_fused(gls_ctx *c, int l, double *x, const double *b, do
   return GLS_OK;
 }
 
+// The prolongation inside the first post-sweep (same level pairs as the fused restriction, and the coarse level a
+// verified hyper_cube lattice too): the fused damped-Jacobi sweep's J.v gathers x + P xc, interpolating each
+// brick's coarse cell in LDS, and hands that value at the brick-surface nodes to the slab sum through the level's
+// scratch vector, so the two transfer launches and their passes over x are not needed. The hard-coded Q2 weights are those checked against the level
+// pair's tap tables at attach (Taps::q2_brick). GLS_MG_FUSE_PROLONG=0 (read per call) or GLS_MG_NO_FUSE keep the
+// separate launches.
+bool mg_fused_prolong_ok(gls_ctx *c, int l) {
+  auto &mg = c->mg;
+  if (l < 0 || l + 1 >= (int)mg.lev.size() || mg.csr || mg.boxed || (size_t)l >= mg.taps.size() || !mg_prolong_add_ok(c, l))
+    return false;
+  const char *e = std::getenv("GLS_MG_FUSE_PROLONG");
+  if (e && std::atoi(e) == 0) return false;
+  gls_ctx *g = mg.lev[(size_t)l], *h = mg.lev[(size_t)l + 1];
+  const auto &T = *mg.taps[(size_t)l];
+  const int64_t nc1 = 2 * (int64_t)g->cube_nb1 + 1;
+  const bool ilu_smooth = mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only;
+  return T.two_pass && T.q2_brick && mg.lpost[(size_t)l] >= 1 && !ilu_smooth && g->smooth_f32 && g->use_brick &&
+         g->use_qdata && !g->use_colors && !g->dist.on && !g->hang.on && !g->oct.on && g->k == 2 && g->cube_nb1 > 0 &&
+         g->cube_nb1 < 1024 && g->use_slab && brick_slab(g) && !g->srf && gls::pencil_enabled() &&
+         gls::brick_fused_jacobi_supported(g->k) && !h->dist.on && !h->hang.on && h->cube_nb1 > 0 &&
+         g->cube_nb1 == 2 * h->cube_nb1 && h->n_vnodes == nc1 * nc1 * nc1 && g->stream == c->stream;
+}
+
 // coarsest level by HIP graph (opt-in, GLS_MG_GRAPH=1: measured at 128^3, 138.0 vs 138.6 ms per
 // Newton step -- the coarse sweeps are bound by the kernels' own latency, not by launch overhead,
 // profiles/r01_coarse_graph_bench.txt): one rank, fused brick sweeps, the level's own b / x buffers (the
@@ -3149,14 +3184,17 @@ int mg_vcycle(gls_ctx *c, int l, const double *b, double *x) {
   // store on one rank: the coarse correction vanishes on the coarse Dirichlet rows (zero rhs rows,
   // D_c-scaled sweeps) and the nested Qk interpolation maps them onto the fine Dirichlet rows, so
   // P xc is exactly 0 there, as the zeroing below makes it in the general path
-  if (mg_prolong_add_ok(c, l)) {
+  const bool pro = mg_fused_prolong_ok(c, l);  // x += P xc inside the first post-sweep's J.v and slab sum
+  if (pro) {  // nothing here: the sweep below gathers x + P xc
+  } else if (mg_prolong_add_ok(c, l)) {
     GLS_TRY(mg_prolong(c, l, xc, x, true));
   } else {
     GLS_TRY(mg_prolong(c, l, xc, y));
     HIP_TRY(gls::vec_set_indexed(y, g->con_dofs.p, nullptr, (int64_t)g->con_dofs.n, s));
     HIP_TRY(gls::vec_axpy(x, 1.0, y, n, s));
   }
-  for (int it = 0; it < mg.lpost[(size_t)l]; ++it) GLS_TRY(smoother_sweep(g, x, b, y, mg.omega, zs));
+  for (int it = 0; it < mg.lpost[(size_t)l]; ++it)
+    GLS_TRY(smoother_sweep(g, x, b, y, mg.omega, zs, pro && it == 0 ? xc : nullptr));
   return GLS_OK;
 }
 
@@ -3424,6 +3462,31 @@ int gls_mg_residual_restrict(gls_ctx *c, int level, const double *x, const doubl
   GLS_TRY(mg_restrict(c, level, y, bc));
   HIP_TRY(gls::vec_set_indexed(bc, h->con_dofs.p, nullptr, (int64_t)h->con_dofs.n, c->stream));
   return GLS_OK;
+}
+
+int gls_mg_prolong_smooth(gls_ctx *c, int level, const double *xc, double *x, const double *b, double omega, int *fused) {
+  GLS_TRY(check_ctx(c));
+  auto &mg = c->mg;
+  if (!mg.on) return set_err(GLS_EINVAL, "gls_mg_prolong_smooth: no multigrid attached");
+  if (level < 0 || level + 1 >= (int)mg.lev.size() || !xc || !x || !b || x == b || omega < 0.0)
+    return set_err(GLS_EINVAL, "gls_mg_prolong_smooth: bad level / pointers / omega");
+  GLS_TRY(mg_prepare(c));  // the levels' states, as the V-cycle sees them
+  gls_ctx *g = mg.lev[(size_t)level];
+  const bool f = mg_fused_prolong_ok(c, level);
+  if (fused) *fused = f ? 1 : 0;
+  double *y = mgbuf(c, level, MB_Y);
+  double *zs = mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only ? mgbuf(c, level, MB_BOX) : nullptr;
+  double *xcw = mgbuf(c, level + 1, MB_X);  // the V-cycle's coarse vector (ghost import writes into it): a copy
+  if (xcw != xc) HIP_TRY(gls::vec_copy(xcw, xc, mg.lev[(size_t)level + 1]->n_dofs, c->stream));
+  if (f) return smoother_sweep(g, x, b, y, omega, zs, xcw);
+  if (mg_prolong_add_ok(c, level)) {
+    GLS_TRY(mg_prolong(c, level, xcw, x, true));
+  } else {
+    GLS_TRY(mg_prolong(c, level, xcw, y));
+    HIP_TRY(gls::vec_set_indexed(y, g->con_dofs.p, nullptr, (int64_t)g->con_dofs.n, c->stream));
+    HIP_TRY(gls::vec_axpy(x, 1.0, y, g->n_dofs, c->stream));
+  }
+  return smoother_sweep(g, x, b, y, omega, zs);
 }
 
 // --------------------------------------------------------------------------------------------

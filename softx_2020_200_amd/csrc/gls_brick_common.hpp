@@ -26,6 +26,29 @@ __device__ __forceinline__ int bnd_index(int X, int Y, int Z) {
   return n - before;
 }
 
+// every third bit of a Morton index: a brick's lattice coordinate (x: v, y: v >> 1, z: v >> 2)
+__device__ __forceinline__ int morton_compact3(unsigned v) {
+  v &= 0x09249249u;
+  v = (v ^ (v >> 2)) & 0x030c30c3u;
+  v = (v ^ (v >> 4)) & 0x0300f00fu;
+  v = (v ^ (v >> 8)) & 0xff0000ffu;
+  return (int)((v ^ (v >> 16)) & 0x3ffu);
+}
+
+// Nested Q2 interpolation of a coarse cell onto the fine brick it contains, one line: the five fine values
+// (local coordinate 0..4) from the line's three coarse values, rows 1 0 0 | 3/8 3/4 -1/8 | 0 1 0 | -1/8 3/4 3/8 | 0 0 1.
+// Even coordinates copy their coarse value; odd ones lie inside this cell only and have one fixed term order. A
+// node shared by several bricks therefore gets the same FP64 value from each of them when every brick applies
+// this function along x, then y, then z: on the shared axis its coordinate is even (0 in one brick, 4 in the
+// other), and both copy the same coarse line.
+__device__ __forceinline__ void q2_prolong_line(double c0, double c1, double c2, double (&o)[5]) {
+  o[0] = c0;
+  o[1] = fma(-0.125, c2, fma(0.75, c1, 0.375 * c0));
+  o[2] = c1;
+  o[3] = fma(0.375, c2, fma(0.75, c1, -0.125 * c0));
+  o[4] = c2;
+}
+
 // LDS hand-off between lanes of ONE wave: LDS ops of a wave execute in order; the asm keeps the
 // compiler from moving LDS accesses across this point.
 __device__ __forceinline__ void wave_sync() {

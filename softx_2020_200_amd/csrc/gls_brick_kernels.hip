@@ -1228,12 +1228,15 @@ __device__ __forceinline__ uint32_t morton3(uint32_t x, uint32_t y, uint32_t z) 
     m |= (((x >> b) & 1u) << (3 * b)) | (((y >> b) & 1u) << (3 * b + 1)) | (((z >> b) & 1u) << (3 * b + 2));
   return m;
 }
-template <typename S, bool J, int K>
+// XS (with J): the sweep's start values are read from xs instead of y (the pencil J.v with the in-kernel
+// prolongation leaves x + P xc of the brick-surface nodes there, OpParams::pxp; y still holds the old x)
+template <typename S, bool J, int K, bool XS = false>
 __global__ void __launch_bounds__(256) k_slab_sum_cube(const S *__restrict__ slab, int nb1, int64_t voff,
                                                        double *__restrict__ y, const uint8_t *__restrict__ vmask,
                                                        const double *__restrict__ jb, const double *__restrict__ jd,
                                                        double jomega, const double *__restrict__ rb,
-                                                       double *__restrict__ x0) {
+                                                       double *__restrict__ x0, const double *__restrict__ xs) {
+  static_assert(!XS || J, "start values: fused Jacobi sweep");
   constexpr int BN = 2 * K + 1, P2 = 2 * K, NBND = BN * BN * BN - (BN - 2) * (BN - 2) * (BN - 2);
   const int NX = P2 * nb1 + 1;
   int bx = blockIdx.x, Z = blockIdx.y;
@@ -1330,7 +1333,7 @@ __global__ void __launch_bounds__(256) k_slab_sum_cube(const S *__restrict__ sla
     const unsigned m = vmask ? vmask[node] : 0u;
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
-      const double x = y[gi[f]], dd = jd[gi[f]];
+      const double x = XS ? xs[gi[f]] : y[gi[f]], dd = jd[gi[f]];
       y[gi[f]] = x + jomega * (jb[gi[f]] - ((f < 3 && ((m >> f) & 1u)) ? dd * x : s[f])) / dd;
     }
   } else if (rb) {
@@ -1348,19 +1351,26 @@ __global__ void __launch_bounds__(256) k_slab_sum_cube(const S *__restrict__ sla
 // nb1 > 0: the structured form (nb1 bricks per direction) instead of the node / offset / slot map
 hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *slabf, int64_t n_vnodes, double *y,
                                const uint8_t *vmask, const double *jb, const double *jd, double jomega, hipStream_t s,
-                               const double *rb, double *x0) {
+                               const double *rb, double *x0, const double *xs) {
   if (nb1 <= 0 || (k != 1 && k != 2)) return hipErrorInvalidValue;
   if (x0 && (!rb || !jd || jb)) return hipErrorInvalidValue;
+  if (xs && (k != 2 || !jb || !jd || xs == y)) return hipErrorInvalidValue;
   const int NX = 2 * k * nb1 + 1;
   const dim3 g((unsigned)(((int64_t)NX * NX + 255) / 256), (unsigned)NX), b(256);
   const int64_t voff = 3 * n_vnodes;
-#define GLS_SLAB_CUBE(KK)                                                                                                   \
+  if (xs) {
+    if (slabf) hipLaunchKernelGGL((k_slab_sum_cube<float, true, 2, true>), g, b, 0, s, slabf, nb1, voff, y, vmask, jb, jd, jomega, rb, x0, xs);
+    else hipLaunchKernelGGL((k_slab_sum_cube<double, true, 2, true>), g, b, 0, s, slab, nb1, voff, y, vmask, jb, jd, jomega, rb, x0, xs);
+    return hipGetLastError();
+  }
+  const double *const no_xs = nullptr;
+#define GLS_SLAB_CUBE(KK)                                                                                                  \
   if (slabf) {                                                                                                              \
-    if (jb) hipLaunchKernelGGL((k_slab_sum_cube<float, true, KK>), g, b, 0, s, slabf, nb1, voff, y, vmask, jb, jd, jomega, rb, x0);  \
-    else hipLaunchKernelGGL((k_slab_sum_cube<float, false, KK>), g, b, 0, s, slabf, nb1, voff, y, vmask, jb, jd, jomega, rb, x0);   \
+    if (jb) hipLaunchKernelGGL((k_slab_sum_cube<float, true, KK>), g, b, 0, s, slabf, nb1, voff, y, vmask, jb, jd, jomega, rb, x0, no_xs);  \
+    else hipLaunchKernelGGL((k_slab_sum_cube<float, false, KK>), g, b, 0, s, slabf, nb1, voff, y, vmask, jb, jd, jomega, rb, x0, no_xs);   \
   } else {                                                                                                                  \
-    if (jb) hipLaunchKernelGGL((k_slab_sum_cube<double, true, KK>), g, b, 0, s, slab, nb1, voff, y, vmask, jb, jd, jomega, rb, x0); \
-    else hipLaunchKernelGGL((k_slab_sum_cube<double, false, KK>), g, b, 0, s, slab, nb1, voff, y, vmask, jb, jd, jomega, rb, x0);  \
+    if (jb) hipLaunchKernelGGL((k_slab_sum_cube<double, true, KK>), g, b, 0, s, slab, nb1, voff, y, vmask, jb, jd, jomega, rb, x0, no_xs); \
+    else hipLaunchKernelGGL((k_slab_sum_cube<double, false, KK>), g, b, 0, s, slab, nb1, voff, y, vmask, jb, jd, jomega, rb, x0, no_xs);  \
   }
   if (k == 1) {
     GLS_SLAB_CUBE(1)

@@ -39,6 +39,9 @@
 #ifndef GLS_PENCIL_NT
 #define GLS_PENCIL_NT 0  // 1: J.v linearization rows read non-temporally (measured slower: 2.61 / 1.36 ms FP64 / FP32 plain vs 2.65 / 1.44 NT)
 #endif
+#ifndef GLS_PENCIL_PRO_XP_LDS
+#define GLS_PENCIL_PRO_XP_LDS 1  // PRO: the brick-interior nodes' x + P xc kept in LDS (0: through P.pxp in memory, measured no faster: 79.1-80.0 vs 78.6-79.5 ms per step)
+#endif
 #ifndef GLS_PENCIL_WPE32
 #define GLS_PENCIL_WPE32 4  // FP32: <= 128 VGPRs -> 4 waves / SIMD
 #endif
@@ -98,11 +101,18 @@ struct PencilTab {
 // brick's 125 nodes (own: the one brick that counts the node's rb) is restricted 5 -> 3 per axis in LDS, in FP64,
 // and stored as the brick's coarse element vector [brick][27][4] (P.slab's buffer; summed per coarse node by
 // k_restrict_sum_cube): no y, no slab entries
-template <typename Real, int MODE, bool GEN, bool FOREST = false, bool OS = false, bool RST = false>
+// PRO: the V-cycle's coarse correction prolongated in front of the fused damped-Jacobi sweep (FP32 J.v on the cube's
+// bricks, P.jx): a brick is one cell of the next-coarser level, so the gather interpolates that cell's 27 nodes
+// (P.pxc) 3 -> 5 per axis in LDS, in FP64, and the sweep starts from xp = x + P xc. Brick-interior nodes store their
+// update of xp; brick-surface nodes are never stored into x here (the neighbouring bricks of this launch still
+// gather the old x there): the brick that owns such a node stores its xp to P.pxp, from where the slab sum starts
+// the node's update. Every brick holding a node forms the same FP64 xp for it (q2_prolong_line)
+template <typename Real, int MODE, bool GEN, bool FOREST = false, bool OS = false, bool RST = false, bool PRO = false>
 __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_PENCIL_WPE32 : GLS_PENCIL_WPE64))
     gls_pencil_kernel(const OpParams P, const PencilTab<Real> T) {
   static_assert(!OS || (MODE == MODE_JVQ && std::is_same<Real, float>::value), "Oseen operator: FP32 J.v only");
   static_assert(!RST || (MODE == MODE_JVQ && std::is_same<Real, float>::value && !FOREST), "restriction: FP32 J.v on the cube");
+  static_assert(!PRO || (MODE == MODE_JVQ && std::is_same<Real, float>::value && !FOREST && !RST), "prolongation: FP32 J.v on the cube");
   using C = PencilCfg<Real, MODE == MODE_JVQ>;
   // MODE_RESLIN = MODE_RESIDUAL + MODE_LIN at one state (assemble_matrix_and_rhs); else MODE_JVQ
   constexpr bool RL = MODE == MODE_RESLIN, RES = MODE == MODE_RESIDUAL || RL, LIN = MODE == MODE_LIN || RL;
@@ -115,6 +125,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   constexpr int CS = C::CS;
   Real *const sO = sS + C::WAVES * C::CPW * CS;                    // [24 cells][OC] cell node values
   int *const sNode = reinterpret_cast<int *>(sO + C::CPG * C::OC);  // [3][BN3P]
+  // PRO: xp of the brick-interior nodes, FP64 [3][27][4] (launch_pencil_jv_prolong asks for these 2592 bytes more)
+  double *const sXP = reinterpret_cast<double *>(sNode + C::BPG * BN3P);
   __shared__ Real sRow[3 * 16];  // V, D, S rows [mat][q][4] for the y sweep's per-lane coefficients
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -156,8 +168,106 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
                                                           : reinterpret_cast<const Real *>(P.qdf);
     qrow = base + qdp_base(brick, valid ? ci : 0, pa + 3 * pb);
   }
-  // ---------------- gather the group's brick nodes: v (masked: P v) or u, p, H, and the node ids
-  for (int t = tid; t < C::BPG * BN3; t += C::THREADS) {
+  // ---------------- PRO: P xc at the nodes of the group's bricks, line by line (q2_prolong_line) along x, y, z. FP64
+  // in LDS areas that are not live yet: the x stage [brick][field][j + 3 k][X] and the y stage [brick][field][k][Y][X]
+  // in the cell-value area, P xc [brick][field][125] in the stage area
+  double *const dPX = reinterpret_cast<double *>(sO), *const dPY = dPX + C::BPG * 4 * 45;
+  double *const dPZ = reinterpret_cast<double *>(sS);
+  if constexpr (PRO) {
+    static_assert((C::BPG * NF * FB) % 2 == 0 && (C::WAVES * C::CPW * CS) % 2 == 0 && (C::CPG * C::OC + C::BPG * BN3P) % 2 == 0 &&
+                      C::WAVES * C::CPW * CS >= 2 * C::BPG * 4 * BN3 && C::CPG * C::OC >= 2 * C::BPG * 4 * (45 + 75),
+                  "prolongation scratch in LDS");
+    static_assert(C::BPG * BN3 <= 2 * C::THREADS, "two brick nodes per thread");
+    // the gather's loads (node id, then x and the mask) are issued first: they are in flight while the stages run
+    int gn[2];
+    unsigned gm[2];
+    double gx[2][4];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi;
+      gn[it] = -1;
+      if (bi < nbg) {
+        const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
+        const int cx = min(X / 2, 1), cy = min(Y / 2, 1), cz = min(Z / 2, 1);
+        const int a = (X - 2 * cx) + 3 * ((Y - 2 * cy) + 3 * (Z - 2 * cz));
+        const int node = P.cell_vnodes[(cell0(brick_of(bi)) + cx + 2 * cy + 4 * cz) * 27 + a];
+        gn[it] = node;
+        gx[it][0] = P.v[(int64_t)node * 3];
+        gx[it][1] = P.v[(int64_t)node * 3 + 1];
+        gx[it][2] = P.v[(int64_t)node * 3 + 2];
+        gx[it][3] = P.v[voff + node];
+        gm[it] = P.vmask ? P.vmask[node] : 0u;
+      }
+    }
+    const int ncx = 2 * P.cube_nb1 + 1;  // coarse lattice nodes per direction
+    double o[5];
+    // x: one thread per (brick, field, coarse line j, k), its three coarse values from the brick's coarse cell
+    for (int t = tid; t < nbg * 36; t += C::THREADS) {
+      const int bf = t / 9, jk = t - 9 * bf, bi = bf >> 2, f = bf & 3, j = jk % 3, k = jk / 3;
+      const unsigned bk = (unsigned)brick_of(bi);
+      const int64_t cn = 2 * morton_compact3(bk) +
+                         (int64_t)ncx * ((2 * morton_compact3(bk >> 1) + j) + (int64_t)ncx * (2 * morton_compact3(bk >> 2) + k));
+      const double *c = f < 3 ? P.pxc + cn * 3 + f : P.pxc + (int64_t)3 * ncx * ncx * ncx + cn;
+      const int st = f < 3 ? 3 : 1;
+      q2_prolong_line(c[0], c[st], c[2 * st], o);
+#pragma unroll
+      for (int X = 0; X < 5; ++X) dPX[bf * 45 + 5 * jk + X] = o[X];
+    }
+    __syncthreads();
+    // y: one thread per (brick, field, k, X)
+    for (int t = tid; t < nbg * 60; t += C::THREADS) {
+      const int bf = t / 15, r = t - 15 * bf, k = r / 5, X = r - 5 * k;
+      const double *x = dPX + bf * 45 + 15 * k + X;
+      q2_prolong_line(x[0], x[5], x[10], o);
+#pragma unroll
+      for (int Y = 0; Y < 5; ++Y) dPY[bf * 75 + 25 * k + 5 * Y + X] = o[Y];
+    }
+    __syncthreads();
+    // z: one thread per (brick, field, Y, X)
+    for (int t = tid; t < nbg * 100; t += C::THREADS) {
+      const int bf = t / 25, yx = t - 25 * bf;
+      const double *y = dPY + bf * 75 + yx;
+      q2_prolong_line(y[0], y[25], y[50], o);
+#pragma unroll
+      for (int Z = 0; Z < 5; ++Z) dPZ[bf * BN3 + 25 * Z + yx] = o[Z];
+    }
+    __syncthreads();
+    // the gather: xp = x + P xc, its masked FP32 cast into the brick arrays
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      if (gn[it] < 0) continue;
+      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi, node = gn[it];
+      const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
+      const double *pz = dPZ + bi * 4 * BN3 + n;
+      const double v0 = gx[it][0] + pz[0], v1 = gx[it][1] + pz[BN3], v2 = gx[it][2] + pz[2 * BN3], vp = gx[it][3] + pz[3 * BN3];
+      if (GLS_PENCIL_PRO_XP_LDS && X > 0 && X < BN - 1 && Y > 0 && Y < BN - 1 && Z > 0 && Z < BN - 1) {  // kept for the node's update
+        typedef double d2 __attribute__((ext_vector_type(2)));
+        d2 *xo = reinterpret_cast<d2 *>(sXP + (bi * 27 + (X - 1) + 3 * ((Y - 1) + 3 * (Z - 1))) * 4);
+        xo[0] = d2{v0, v1};
+        xo[1] = d2{v2, vp};
+      } else {
+        // a brick-surface node: x keeps its old value (the other bricks holding the node gather it in this
+        // launch); the one brick that owns the node (restrict_store's rule) hands xp to the slab sum in P.pxp
+        const unsigned bk = (unsigned)brick_of(bi);
+        const int top = P.cube_nb1 - 1;
+        if ((X < BN - 1 || morton_compact3(bk) == top) && (Y < BN - 1 || morton_compact3(bk >> 1) == top) &&
+            (Z < BN - 1 || morton_compact3(bk >> 2) == top)) {
+          P.pxp[(int64_t)node * 3] = v0;
+          P.pxp[(int64_t)node * 3 + 1] = v1;
+          P.pxp[(int64_t)node * 3 + 2] = v2;
+          P.pxp[voff + node] = vp;
+        }
+      }
+      Real *b = sB + bi * NF * FB + X + SY * Y + SZ * Z;
+      b[0] = (gm[it] & 1u) ? Real(0) : (Real)v0;
+      b[FB] = (gm[it] & 2u) ? Real(0) : (Real)v1;
+      b[2 * FB] = (gm[it] & 4u) ? Real(0) : (Real)v2;
+      b[3 * FB] = (Real)vp;
+      sNode[bi * BN3P + n] = node;
+    }
+  }
+  // ---------------- gather the group's brick nodes: v (masked: P v) or u, p, H, and the node ids (PRO: done above)
+  for (int t = tid; t < (PRO ? 0 : C::BPG * BN3); t += C::THREADS) {
     const int bi = t / BN3, n = t % BN3;
     if (bi >= nbg) break;
     const int brick = brick_of(bi);
@@ -366,7 +476,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
 #pragma unroll
           for (int f = 0; f < 4; ++f) {
             const bool con = f < 3 && ((m >> f) & 1u);
-            const double x = P.jx[gi[f]], dd = P.jd[gi[f]];
+            const double x = !PRO ? P.jx[gi[f]] : GLS_PENCIL_PRO_XP_LDS ? sXP[(rb_ * 27 + (Xn - 1) + 3 * ((Yn - 1) + 3 * (Zn - 1))) * 4 + f] : P.pxp[gi[f]];
+            const double dd = P.jd[gi[f]];
             P.jx[gi[f]] = x + P.jomega * (P.jb[gi[f]] - (con ? dd * x : (double)s[f])) / dd;
           }
         } else if (fused && P.rb) {
@@ -417,13 +528,6 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
       c1 = r2 + 0.75 * (r1 + r3);
       c2 = r4 + (0.375 * r3 - 0.125 * r1);
     };
-    auto compact3 = [](unsigned v) {  // every third bit of a Morton index
-      v &= 0x09249249u;
-      v = (v ^ (v >> 2)) & 0x030c30c3u;
-      v = (v ^ (v >> 4)) & 0x0300f00fu;
-      v = (v ^ (v >> 8)) & 0xff0000ffu;
-      return (int)((v ^ (v >> 16)) & 0x3ffu);
-    };
     // FP64 from here on (the residual's rb - s and the restriction as the separate FP64 launches form them: the
     // two paths differ by FP64 summation order only). LDS, all dead by now: r [brick][field][125] and the y
     // sweep's output in the brick-field + stage areas, the x sweep's output in the cell-value area
@@ -460,8 +564,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
       // a node on a face shared by two bricks belongs to the upper one (local coordinate 0); the domain's
       // upper faces to their only brick
       const int top = P.cube_nb1 - 1;
-      const bool own = (Xn < BN - 1 || compact3((unsigned)bk) == top) && (Yn < BN - 1 || compact3((unsigned)bk >> 1) == top) &&
-                       (Zn < BN - 1 || compact3((unsigned)bk >> 2) == top);
+      const bool own = (Xn < BN - 1 || morton_compact3((unsigned)bk) == top) && (Yn < BN - 1 || morton_compact3((unsigned)bk >> 1) == top) &&
+                       (Zn < BN - 1 || morton_compact3((unsigned)bk >> 2) == top);
       const unsigned m = P.vmask ? P.vmask[node] : 0u;  // constrained rows restrict onto constrained coarse rows only: 0
       double r[4] = {-(double)s[0], -(double)s[1], -(double)s[2], -(double)s[3]};
       if (own) {
@@ -942,6 +1046,35 @@ hipError_t launch_pencil_jv_restrict(const OpParams &P, const Tables1D &T, hipSt
   else
     hipLaunchKernelGGL((gls_pencil_kernel<float, MODE_JVQ, false, false, false, true>), dim3((unsigned)n_groups), dim3(256),
                        pencil_lds_bytes<float>(MODE_JVQ), s, P, tab);
+  return hipGetLastError();
+}
+// fused damped-Jacobi sweep from x + P xc (P.jx = P.v = x, P.pxc = xc on the next-coarser nested level of
+// P.cube_nb1 cells per direction): brick-interior nodes are stored here, brick-surface nodes by
+// brick_slab_sum_cube from their x + P xc in P.pxp; no SRF terms
+hipError_t launch_pencil_jv_prolong(const OpParams &P, const Tables1D &T, hipStream_t s) {
+  if (P.n_probe > 0 || P.bricks || P.subset || P.brick_cell0 || P.srf || !(P.slab || P.slabf) || !P.qdf || !P.pxc || !P.pxp || P.pxp == P.jx || !P.jx ||
+      P.jx != P.v || !P.jb || !P.jd || P.rb || P.jx0 || P.ev || P.cube_nb1 <= 0 || P.cube_nb1 > 1023 ||
+      (int64_t)P.cube_nb1 * P.cube_nb1 * P.cube_nb1 * 8 != P.n_cells)
+    return hipErrorNotSupported;
+  const int n_groups = (P.n_cells / 8 + 2) / 3;
+  PencilTab<float> tab;
+  for (int q = 0; q < 3; ++q) {
+    tab.w[q] = (float)T.w[q];
+    for (int i = 0; i < 3; ++i) {
+      tab.V[q][i] = (float)T.V[q][i];
+      tab.D[q][i] = (float)T.D[q][i];
+      tab.S[q][i] = (float)T.S[q][i];
+    }
+    tab.xi[q] = (float)T.xi[q];
+  }
+  // the plain launch's LDS and the brick-interior nodes' xp [3][27][4] in FP64
+  const size_t lds = pencil_lds_bytes<float>(MODE_JVQ) + (GLS_PENCIL_PRO_XP_LDS ? sizeof(double) * PencilCfg<float, true>::BPG * 27 * 4 : 0);
+  if (P.oseen)
+    hipLaunchKernelGGL((gls_pencil_kernel<float, MODE_JVQ, false, false, true, false, true>), dim3((unsigned)n_groups),
+                       dim3(256), lds, s, P, tab);
+  else
+    hipLaunchKernelGGL((gls_pencil_kernel<float, MODE_JVQ, false, false, false, false, true>), dim3((unsigned)n_groups),
+                       dim3(256), lds, s, P, tab);
   return hipGetLastError();
 }
 hipError_t launch_pencil_residual(const OpParams &P, const Tables1D &T, hipStream_t s) {

@@ -117,7 +117,14 @@ struct OpParams {
   // with the same code)
   double *cq;
   int cq_mode;
-  int cube_nb1;               // pencil J.v with the in-kernel restriction: bricks per direction of the hyper_cube
+  int cube_nb1;               // pencil J.v with the in-kernel restriction / prolongation: bricks per direction of
+                              //   the hyper_cube (= cells per direction of the next-coarser nested level)
+  // with jx (FP32 pencil J.v on the cube, hyper_cube slab sum): the V-cycle's coarse correction prolongated in
+  // front of the fused damped-Jacobi sweep: the sweep starts from xp = jx + P pxc, formed in the gather. pxc: the
+  // next-coarser level's vector, lexicographic lattice of 2 cube_nb1 + 1 nodes. Brick-interior nodes store their
+  // update; pxp (a vector other than jx) receives xp at the brick-surface nodes, which the slab sum updates
+  const double *pxc;
+  double *pxp;
 };
 
 }  // namespace gls

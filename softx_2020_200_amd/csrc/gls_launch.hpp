@@ -30,6 +30,11 @@ hipError_t launch_pencil_jv(const OpParams &P, const Tables1D &T, hipStream_t s,
 // kernel (hyper_cube, Morton bricks): rb - A v per brick, restricted 5 -> 3 per axis, as coarse element
 // vectors [brick][27][4] (FP64) in P.slab's buffer; nothing goes to y. hipErrorNotSupported when not applicable
 hipError_t launch_pencil_jv_restrict(const OpParams &P, const Tables1D &T, hipStream_t s);
+// FP32 J.v of the V-cycle's first post-sweep with the prolongation from the next-coarser nested level inside the
+// kernel (hyper_cube, Morton bricks): the fused damped-Jacobi sweep (P.jx) starts from x + P xc (P.pxc, coarse
+// lattice of P.cube_nb1 cells per direction); x + P xc at the brick-surface nodes goes to P.pxp, which the slab
+// sum that follows takes as its start values. hipErrorNotSupported when not applicable
+hipError_t launch_pencil_jv_prolong(const OpParams &P, const Tables1D &T, hipStream_t s);
 hipError_t launch_pencil_residual(const OpParams &P, const Tables1D &T, hipStream_t s);  // MODE_RESIDUAL, FP64
 hipError_t launch_pencil_lin(const OpParams &P, const Tables1D &T, hipStream_t s);  // MODE_LIN (+ diagonal into P.y)
 // MODE_RESLIN: residual (res_y / res_slab) + linearization (qd, qdf) + diagonal (y / slab) in one pass
@@ -56,7 +61,9 @@ hipError_t brick_slab_sum_ex(const double *slab, const float *slabf, const int32
 // bricks, no periodic wrap): slots computed from the lattice coordinates, no index arrays
 hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *slabf, int64_t n_vnodes, double *y,
                                const uint8_t *vmask, const double *jb, const double *jd, double jomega, hipStream_t s,
-                               const double *rb = nullptr, double *x0 = nullptr);  // x0: OpParams::jx0's surface nodes
+                               const double *rb = nullptr, double *x0 = nullptr,  // x0: OpParams::jx0's surface nodes
+                               const double *xs = nullptr);  // xs (k = 2, with jb): the sweep's start values instead
+                                                             //   of y's (launch_pencil_jv_prolong's OpParams::pxp)
 // coarse right-hand side from the bricks' restricted residuals (launch_pencil_jv_restrict: ev [brick][27][4],
 // nb1 fine bricks = coarse cells per direction): bc[node] = sum of the node's <= 8 element-vector entries in
 // ascending (Morton brick, local node) order, rows in the coarse vmask zeroed; n_vnodes = (2 nb1 + 1)^3

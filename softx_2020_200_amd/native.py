@@ -32,7 +32,7 @@ EXPORTS = [
     "gls_part_create", "gls_part_sizes", "gls_part_get", "gls_part_destroy", "gls_dist_attach", "gls_dist_import", "gls_rccl_unique_id", "gls_rccl_create", "gls_rccl_destroy", "gls_rccl_info", "gls_mg_smoother_apply", "gls_mg_attach_replica",
     "gls_dist_attach_rccl",
     "gls_mg_attach", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
-    "gls_mg_residual_restrict",
+    "gls_mg_residual_restrict", "gls_mg_prolong_smooth",
     "gls_prm_parse", "gls_prm_get", "gls_prm_n_entries", "gls_prm_entry", "gls_prm_destroy",
     "gls_expr_create", "gls_expr_n_components", "gls_expr_eval", "gls_expr_destroy",
     "gls_vtu_write", "gls_pvtu_write", "gls_pvd_write",
@@ -196,6 +196,7 @@ def load():
                                         C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.gls_mg_transfer.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.gls_mg_residual_restrict.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+    L.gls_mg_prolong_smooth.argtypes = [vp, C.c_int, vp, vp, vp, C.c_double, C.POINTER(C.c_int)]
     P64 = C.POINTER(i64)
     L.gls_set_hanging.argtypes = [vp, i64, P64, P64, P64, d]
     L.gls_mesh_refined_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
@@ -1022,6 +1023,16 @@ class GLSContext:
         check(self.L.gls_mg_residual_restrict(self.h, int(level), _ptr(x), _ptr(b), _ptr(out), C.byref(fused)),
               "gls_mg_residual_restrict")
         return out, bool(fused.value)
+
+    def mg_prolong_smooth(self, level, xc, x, b, omega):
+        """The V-cycle's prolongation and first post-sweep on level: x <- S(x + P xc) in place, one smoothing
+        sweep of damping omega for the right-hand side b (gls_mg_prolong_smooth). Returns (x, fused): fused is
+        True when the coarse correction was interpolated inside the sweep's launches, False for the separate
+        transfer launches."""
+        fused = C.c_int(0)
+        check(self.L.gls_mg_prolong_smooth(self.h, int(level), _ptr(xc), _ptr(x), _ptr(b), float(omega),
+                                           C.byref(fused)), "gls_mg_prolong_smooth")
+        return x, bool(fused.value)
 
     def set_lattice(self, n1d, local_to_global):
         """Declare the (rank-local) nodes as a box of the global n1d^3 hyper_cube node lattice."""
