@@ -346,6 +346,20 @@ int gls_ilu_factors(gls_ctx *ctx, int32_t *perm, int32_t *rowp, int32_t *col, do
  * to get out_nnz; capacity = length of out_col / out_level. */
 int gls_iluk_pattern(int64_t n, const int32_t *rowp, const int32_t *col, int fill, int32_t *out_rowp,
                      int32_t *out_col, int32_t *out_level, int64_t capacity, int64_t *out_nnz);
+/* Host only (no device): the plan gls_ilu_attach computes on one rank from the mesh and the constraints alone.
+ * Inputs as gls_create takes them (cell_pnodes NULL: the pressure sits on the velocity nodes), the constrained
+ * DoFs (the Dirichlet mask's DoFs and the lines' DoFs) and the lines of gls_set_hanging without their weights;
+ * fill, ordering, block_dofs as gls_ilu_attach / gls_ilu_set_options. Outputs (each may be NULL): perm[dof] = its
+ * row; rowp [n_dofs + 1] / col (capacity entries) of the ILU(fill) pattern; probe[dof] = the probe vector that
+ * holds the DoF's unit entry; color[dof] = its colour in the multicolor order (-1 in the Cuthill-McKee order);
+ * out_nnz / out_nnz_a = entries of the ILU pattern / of the system matrix; out_n_probes; out_mc_solve = 1 when the
+ * color-by-color solves apply. Call with perm, rowp, col, probe and color all NULL to get the counts. */
+int gls_ilu_plan(int dim, int k, int kp, int64_t n_vnodes, int64_t n_pnodes, int64_t n_cells, const int32_t *cell_vnodes,
+                 const int32_t *cell_pnodes, int64_t n_con, const int64_t *con_dofs, int64_t n_lines,
+                 const int64_t *line_dofs, const int64_t *line_offsets, const int64_t *line_masters, int fill,
+                 int ordering, int64_t block_dofs, int32_t *perm, int32_t *rowp, int32_t *col, int64_t capacity,
+                 int32_t *probe, int32_t *color, int64_t *out_nnz, int64_t *out_nnz_a, int *out_n_probes,
+                 int *out_mc_solve);
 /* Host only: the DoF renumbering gls_ilu_attach uses (deal.II DoFRenumbering::Cuthill_McKee,
  * gls_navier_stokes.cc:70) on a node graph: node x's row nodes adj[adj_off[x] .. adj_off[x+1]) (itself
  * included), its DoFs dofs[dof_off[x] .. dof_off[x+1]) (old order = position in dofs);

@@ -22,8 +22,7 @@
 #include <vector>
 
 #include "../../include/gls_native.h"
-
-int gls_io_set_error(int code, const char *fmt, ...);  // gls_api.cpp
+#include "gls_error.hpp"
 
 namespace {
 

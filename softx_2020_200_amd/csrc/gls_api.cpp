@@ -1,5 +1,8 @@
-// gls_api.cpp — C-ABI implementation: context lifecycle, operator dispatch, GMRES, Newton,
-// hyper_cube mesh and time-integration coefficients. Host C++17 over HIP.
+// gls_api.cpp — C-ABI implementation: context lifecycle, operator dispatch, multigrid, GMRES / BiCGStab, Newton,
+// hyper_cube mesh and time-integration coefficients; the last-error string. Host C++17 over HIP. The context struct
+// and the helpers shared with the other host files: gls_ctx.hpp; the assembled ILU: gls_ilu.cpp (its host-only
+// plan: gls_ilu_plan.cpp); Kelly, boundary loads, flow diagnostics and device output: gls_postproc.cpp; the RCCL
+// transport: gls_rccl.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,20 +21,17 @@
 #include <set>
 #include <thread>
 
-#include <rocblas/rocblas.h>
-#include <rocsolver/rocsolver.h>
-#include <rocsparse/rocsparse.h>
-#include <rccl/rccl.h>
+#include "gls_ctx.hpp"
 
-#include "../../include/gls_native.h"
-#include "gls_common.hpp"
-#include "gls_launch.hpp"
-#include "gls_sparse.hpp"
+using namespace gls_impl;
 
 namespace {
 
 thread_local std::string g_err;
 
+}  // namespace
+
+namespace gls_impl {  // declared in gls_ctx.hpp
 int set_err(int code, const char *fmt, ...) {
   char buf[1024];
   va_list ap;
@@ -41,54 +41,9 @@ int set_err(int code, const char *fmt, ...) {
   g_err = buf;
   return code;
 }
+}  // namespace gls_impl
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return set_err(GLS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-#define GLS_TRY(expr)          \
-  do {                         \
-    int r_ = (expr);           \
-    if (r_ < 0) return r_;     \
-  } while (0)
-
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-  DevBuf &operator=(DevBuf &&o) noexcept {
-    if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  int alloc(size_t count) {
-    release();
-    if (count == 0) return GLS_OK;
-    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) {
-      p = nullptr;
-      return set_err(GLS_ENOMEM, "hipMalloc of %zu bytes failed", count * sizeof(T));
-    }
-    n = count;
-    return GLS_OK;
-  }
-  int upload(const T *h, size_t count) {
-    GLS_TRY(alloc(count));
-    if (count && hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_err(GLS_EHIP, "upload failed");
-    return GLS_OK;
-  }
-};
+namespace {
 
 // ---------------- time coefficients (host) ----------------
 // Variable-step BDF via divided differences of the backward time levels
@@ -111,7 +66,7 @@ bool is_sdirk(int s) { return s >= GLS_SDIRK2 && s <= GLS_SDIRK3_3; }
 }  // namespace
 
 int gls_internal_set_err(int code, const char *msg) { return set_err(code, "%s", msg); }
-int gls_io_set_error(int code, const char *fmt, ...) {  // gls_io.cpp
+int gls_io_set_error(int code, const char *fmt, ...) {
   char buf[1024];
   va_list ap;
   va_start(ap, fmt);
@@ -184,6 +139,8 @@ void legendre_pd(int n, double x, double &P, double &dP) {
   dP = n * (x * p1 - p0) / (x * x - 1.);
 }
 
+}  // namespace
+namespace gls_impl {  // declared in gls_ctx.hpp
 // QGauss(n) on [0,1]: Newton on the Legendre roots, ascending.
 void gauss_points(int n, double *x, double *w) {
   for (int i = 0; i < n; ++i) {
@@ -242,6 +199,8 @@ void lagrange_1d(int k, const double *xn, int i, double s, double &v, double &d,
     }
   }
 }
+}  // namespace gls_impl
+namespace {
 
 gls::Tables1D make_tables(int k, int kp, int nq1d) {
   gls::Tables1D T;
@@ -263,433 +222,6 @@ gls::Tables1D make_tables(int k, int kp, int nq1d) {
 }
 
 }  // namespace
-
-// ============================================================================================
-// context
-// ============================================================================================
-struct gls_ctx {
-  int dim = 0, k = 0, kp = 0, nq1d = 0, n_cells = 0, n_vnodes = 0, n_pnodes = 0, nq = 0;
-  int64_t n_dofs = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  gls::Tables1D tables;
-  DevBuf<int32_t> cell_vnodes, cell_pnodes;
-  DevBuf<int32_t> face_nbr;  // [n_cells][2 dim] face neighbours (Kelly), built on first use
-  DevBuf<double> geo, x0, force_q;
-  DevBuf<double> gq;               // mapped cells: per-q geometry [n_cells][nq][kGeo] (nullptr: boxes)
-  // gls_flow_diagnostics, allocated at its first call: cell->measure(), the 1D tables, block partials, result
-  DevBuf<double> fd_meas, fd_tab, fd_partial, fd_out;
-  std::vector<double> host_x0, host_h, host_support;  // host geometry for gls_quadrature_points
-  int map_degree = 0;
-  DevBuf<uint8_t> vmask;
-  DevBuf<int64_t> con_dofs;  // zero_constraints DoF list
-  DevBuf<int64_t> dir_dofs;  // nonzero_constraints (Dirichlet) list
-  DevBuf<double> dir_vals;
-  double viscosity = 1.0;
-  int srf = 0;
-  double omega[3] = {0, 0, 0};
-  // time state
-  int scheme = GLS_STEADY;
-  double alpha[4] = {0, 0, 0, 0}, alpha_jac = 0., sdt2 = 0.;
-  int n_hist = 0;
-  // evaluation state (borrowed device pointers)
-  const double *u = nullptr, *u1 = nullptr, *u2 = nullptr, *u3 = nullptr;
-  DevBuf<double> diag;  // diagonal at the current state (also D_c for constrained rows)
-  bool diag_valid = false;
-  DevBuf<double> qdata;   // brick J.v linearization at the quadrature points (MODE_LIN output)
-  bool qd_valid = false;  // invalidated with the diagonal by every state / parameter change
-  // per-cell kernels: linearization cache (u, grad u, tau, R_s per quadrature point) written by the diagonal
-  // pass and read by the J.v (OpParams::cq); valid with qd_valid's rules
-  DevBuf<double> cq;
-  bool cq_valid = false;
-  DevBuf<float> qdata32;  // FP32 copy of qdata: the multigrid smoother's J.v (mixed precision)
-  bool qd32_valid = false;  // stale whenever qdata is recomputed
-  bool qd32_partial = false;  // the FP32 copy holds only u and tau (written for the Oseen smoother operator)
-  // per-cell path: element vectors and each node's slots in them (deterministic scatter)
-  DevBuf<double> ev;
-  DevBuf<double> bev;  // batched ILU probing: element vectors of a batch of probe vectors
-  DevBuf<uint8_t> bact;  // ... and which (probe, cell batch) blocks computed them
-  DevBuf<int64_t> ev_voff, ev_vslot, ev_poff, ev_pslot;
-  bool smooth_f32 = false;  // this level's V-cycle J.v runs in FP32 (gls_mg_params.mixed_precision)
-  bool smooth_oseen = false;  // ... with the Oseen (Picard) operator (gls_mg_params.smoother_operator = 1)
-  bool use_qdata = true;  // GLS_JV_RECOMPUTE=1 -> J.v recomputes the state per call (MODE_JV)
-  // solver workspace
-  DevBuf<double> work, scal, coef;  // multidot partials, device dot results, GMRES coefficients
-  DevBuf<double> scal2;  // GMRES: the projection pass's dots (scal holds the coefficients it reads)
-  double *hpin = nullptr;  // pinned host copy of the Gram-Schmidt dots (async D2H, one wait per pass pair)
-  size_t hpin_n = 0;
-  DevBuf<double> krylov;      // (restart+1) x n_dofs
-  DevBuf<double> zbasis;      // restart x n_dofs: M^-1 v_j when the preconditioner is the V-cycle
-  DevBuf<double> bicg;        // 7 x n_dofs BiCGStab work vectors (when the GMRES basis is smaller)
-  int krylov_m = 0;
-  DevBuf<double> tmp1, tmp2, tmp3, tmp4, tmp5;
-  bool use_brick = false;  // sum-factorized brick kernels (3D Qk-Qk, Morton 2x2x2 bricks)
-  // brick-boundary node sums without atomics: each brick stores its partial sums of its NBND
-  // surface nodes into a slab; k_slab_sum adds a node's slots in a fixed order (CSR node -> slots)
-  bool use_slab = false;
-  DevBuf<double> slab;
-  DevBuf<double> slab2;  // the fused residual + linearization pass: the residual's brick-surface slab
-  DevBuf<int32_t> sum_nodes, sum_off, sum_slots;
-  int cube_nb1 = 0;  // > 0: the mesh is the structured hyper_cube with cube_nb1 bricks per direction
-                     // (k_slab_sum_cube computes the slab slots from the lattice; GLS_SLAB_CSR=1: off)
-  // colored brick launches (opt-in GLS_BRICK_COLORS=1): bricks greedily colored in Morton order so
-  // that no two bricks of a color share a node (the 2x2x2 parity classes on a brick lattice: 8
-  // colors); surface-node sums carried across colors in acc, no slab and no k_slab_sum. Measured
-  // slower at Q2 128^3 (profiles/r02_brick_colors_ab.txt: J.v 3.66 vs 3.00 + 0.55 ms, FP32 3.18 vs
-  // 2.44 + 0.45 ms): a color's bricks are not neighbours, so the surface nodes neighbouring bricks
-  // share are fetched again from HBM by the later colors instead of hitting L2.
-  bool use_colors = false;
-  int n_colors = 0;
-  int color_off[17] = {0};
-  DevBuf<int32_t> color_bricks;
-  DevBuf<uint16_t> ncolor;
-  DevBuf<double> acc;  // running sums for the fused Jacobi sweep (which stores x, not A x)
-  // distributed (rank-local mesh): owned nodes [0, n_owned), ghosts after; exchange via callbacks
-  struct Dist {
-    bool on = false;
-    // dofs: DoF-level exchange of a general mesh (gls_dist_attach_dofs: one double per DoF, owned
-    // velocity nodes [0, n_owned) and owned pressure nodes [0, n_owned_p) first); else node-level
-    // exchange of a Morton brick mesh (4 doubles per node)
-    bool dofs = false;
-    int width = 4;  // doubles per exchange entry
-    int64_t n_owned = 0, n_owned_p = 0, n_send = 0, n_recv = 0;
-    DevBuf<int32_t> add_u, add_off, add_slot;  // export-add (node or DoF exchange) in a fixed order
-    DevBuf<int32_t> send_nodes, recv_nodes;
-    double *send_buf = nullptr, *recv_buf = nullptr, *red_buf = nullptr;
-    gls_exchange_fn xchg = nullptr;
-    gls_allreduce_fn allreduce = nullptr;
-    void *user = nullptr;
-    // in-library RCCL transport (gls_dist_attach_rccl): grouped ncclSend / ncclRecv and ncclAllReduce
-    // enqueued on the context stream -- no host callback, no host synchronisation per exchange
-    ncclComm_t comm = nullptr;
-    std::vector<int> nbrs;
-    std::vector<int64_t> soff, roff;
-    std::vector<int32_t> h_send, h_recv;  // host copies of the DoF exchange lists (gls_dist_attach_dofs)
-    std::vector<int64_t> h_soff, h_roff;
-    DevBuf<double> own_send, own_recv, own_red;
-    // overlap of the J.v ghost import with the interior bricks (RCCL transport): exchange stream
-    hipStream_t xstream = nullptr;
-    hipEvent_t ev_ready = nullptr, ev_done = nullptr;
-  } dist;
-  // brick split for the overlapped J.v: bricks touching a ghost or exported node first
-  // (split[0 .. split_bnd)), then the interior bricks (split[split_bnd .. split_bnd + split_int))
-  DevBuf<int32_t> split;
-  int split_bnd = 0, split_int = 0;
-  // assembled ILU(0) preconditioner (gls_ilu_attach; the reference's setup_ILU,
-  // gls_navier_stokes.cc:1161-1176): the Jacobian is assembled into CSR by probing the matrix-free
-  // operator with distance-2-colored unit vectors, perturbed on the diagonal like Ifpack (athresh,
-  // rthresh) and factored in place by rocSPARSE; M^-1 v = U^-1 L^-1 v (two sparse triangular solves)
-  struct ILU {
-    bool on = false, valid = false;
-    // attached by the multigrid for its coarse matrix's probing pattern only (mg_probe_setup): never factored or
-    // applied as a preconditioner / smoother of this context
-    bool probe_only = false;
-    double athresh = 0., rthresh = 1.;
-    double boost_tol = 0., boost_val = 0.;  // rocsparse keeps these POINTERS and reads them in csrilu0
-    int n_probes = 0, fill = 0;
-    int64_t block_dofs = 0;  // subdomain size of the block-Jacobi ILU (gls_ilu_set_options); 0: one block
-    int ordering = GLS_ILU_ORDER_CM, n_blocks = 1, n_order_colors = 0;
-    // multicolor order with a pattern whose same-color entries stay inside a node (fill 0): the
-    // color-by-color solves of gls_ilu_kernels.hip replace rocSPARSE csrsv
-    bool mc_solve = false;
-    bool mc_factor = false;  // multicolor order: color-by-color numeric factorization (no rocSPARSE csrilu0)
-    bool mc_compact = false;  // ... by the compact-LDS kernel (rows <= kIluCompactRow)
-    DevBuf<double> rdiag;     // ... its 1 / U_ii per row
-    std::vector<uint8_t> mc_wl, mc_wu;  // per color: wavefronts per node group in the lower / upper solve
-    DevBuf<int64_t> mc_desc;   // per node group: the solves' descriptor (gls::kGroupDesc int64)
-    DevBuf<int64_t> mc_moff;   // factorization position map: per row, its first entry
-    DevBuf<uint16_t> mc_map;   // per (row, pivot, upper entry of the pivot row): position in the row
-    std::vector<int32_t> mc_cg;          // per color: first node group (host, n_colors + 1)
-    DevBuf<int32_t> mc_grow;             // node group -> first row
-    DevBuf<int64_t> mc_lsp, mc_usp;      // per row: L / U split entries
-    DevBuf<int64_t> ghost_diag;          // across ranks: diagonal entries of the ghost (identity) rows
-    // across ranks, complete owned rows: the neighbours' cell contributions to the owned x owned block
-    // arrive per probe round through the export exchange (n_rounds = the largest probe count of any
-    // rank); round p adds send_buf slots into CSR entries ru[rr[p] .. rr[p+1]) in a fixed order
-    bool complete = false;
-    int n_rounds = 0;
-    std::vector<int64_t> rr;
-    DevBuf<int64_t> ru;
-    DevBuf<int32_t> ruoff, rslot;
-    std::vector<int64_t> pdoff, peoff;   // per probe: offsets into pdofs and (pent, prow)
-    DevBuf<int32_t> pdofs, prow;         // probe unit DoFs; the rows of the CSR entries filled by the probe
-    DevBuf<int64_t> pent;                // those entries (positions: 64-bit, the fine levels pass 2^31 entries)
-    DevBuf<int32_t> pdpid, pepid;        // probe of each unit DoF / each extracted entry (batched probing)
-    DevBuf<double> bV, bC, bY;           // batched probing: probe vectors, C V (hanging lines), results [batch][n_dofs]
-    // batched probing's activity: which (probe, cell batch) pairs have a nonzero C e_p on their cells depends on
-    // the pattern and the hanging lines only, so the first probing records it (the kernel's flags, wact) and the
-    // later ones launch just the active pairs (wlist, per chunk from woff; chunk size wB, batches wnblk)
-    DevBuf<uint8_t> wact;
-    DevBuf<int32_t> wlist;
-    std::vector<int64_t> woff;
-    int wB = 0;
-    int64_t wnblk = 0;
-    // CSR pattern (Cuthill-McKee or multicolor order), diagonal entry per row: 64-bit positions (a 13 M-DoF Q2-Q1
-    // level has ~2.9e9 entries); rowp32: the 32-bit row pointers rocSPARSE takes, when the pattern fits them
-    DevBuf<int64_t> rowp, didx;
-    DevBuf<int32_t> col, rowp32;
-    DevBuf<int32_t> perm;                // DoF -> its row in the factored (renumbered) matrix
-    DevBuf<double> val, vbuf, ybuf, tbuf;
-    DevBuf<char> work;
-    rocsparse_handle h = nullptr;
-    rocsparse_mat_descr dA = nullptr, dL = nullptr, dU = nullptr;
-    rocsparse_mat_info info = nullptr;
-    int64_t nnz = 0, nnz_a = 0;  // entries of the ILU(fill) pattern / of the system matrix
-    void release() {
-      if (info) rocsparse_destroy_mat_info(info);
-      if (dA) rocsparse_destroy_mat_descr(dA);
-      if (dL) rocsparse_destroy_mat_descr(dL);
-      if (dU) rocsparse_destroy_mat_descr(dU);
-      if (h) rocsparse_destroy_handle(h);
-      info = nullptr;
-      dA = dL = dU = nullptr;
-      h = nullptr;
-    }
-    ~ILU() { release(); }
-  } ilu;
-  // hanging-node constraints (gls_set_hanging): lines dof <- sum w * master
-  struct Hang {
-    bool on = false;
-    DevBuf<int64_t> dof, off, master, ooff, omaster;  // all lines; operator lines (Dirichlet masters dropped)
-    DevBuf<double> w, ow;
-    DevBuf<int64_t> tm, toff, tdof;                     // operator lines transposed: master -> (hanging dof, w)
-    DevBuf<double> tw;
-    DevBuf<uint8_t> hmask;                             // hanging velocity components per node
-    DevBuf<uint8_t> dmask;                             // 1 on the hanging DoFs (C v in one pass)
-    DevBuf<double> vbuf;                               // C v for J.v
-    std::vector<int64_t> h_dof, h_off, h_master;       // host copy of the lines (ILU sparsity)
-  } hang;
-  // adapted forests (hanging contexts, 3D Q2-Q2 boxes): the complete sibling groups of leaves run the
-  // pencil kernel (cached linearization, element-vector output), the other cells the per-cell kernel
-  struct Oct {
-    bool on = false;
-    int nb = 0;
-    DevBuf<int32_t> cell0, list;  // first cell of each brick; 0..nb-1 (the launch's brick list)
-    DevBuf<int32_t> rest;         // the cells outside the bricks (the per-cell kernel's list)
-    int n_rest = 0;
-    bool f32_next = false;        // the next J.v: the bricks in FP32 from qdata32 (the V-cycle's smoother)
-  } oct;
-  // embedding in the global hyper_cube node lattice (gls_set_lattice): box of local nodes
-  struct Lattice {
-    bool set = false;
-    int n1d = 0, box0[3] = {0, 0, 0}, bdim[3] = {0, 0, 0};
-    DevBuf<int32_t> map;  // box node (x fastest) -> local node
-  } lat;
-  // geometric multigrid preconditioner (levels[0] == this context)
-  struct MG {
-    bool on = false;
-    bool boxed = false;    // distributed levels: transfers go through box gather / scatter
-    std::vector<gls_ctx *> lev;
-    std::vector<std::array<int, 3>> dims;  // box lattice nodes per direction per level
-    int k = 2, pre = 2, post = 2, csweeps = 30;
-    std::vector<int> lpre, lpost;  // per-level sweep counts (default pre / post)
-    double omega = 0.6, comega = 0.6;
-    std::vector<std::unique_ptr<DevBuf<double>>> bufs;  // per level l>=1: u,u1,u2,u3,b,x,y ; level 0: y
-    // per level pair (l, l+1) and axis: 1D tap tables [n_out][5] of prolongation / restriction
-    struct Taps {
-      DevBuf<int32_t> pi[3], ri[3], pc[3], rc[3];
-      DevBuf<double> pw[3], rw[3];
-      bool two_pass = false;  // the xy tiles of mg_transfer_2pass fit these tables
-      // Q2: every axis' taps are the brick-local 5 <-> 3 table the pencil J.v's in-kernel restriction uses
-      // (fine nodes 4 c .. 4 c + 4 from coarse nodes 2 c .. 2 c + 2: 1 | 3/8 3/4 -1/8 | 1 | -1/8 3/4 3/8 | 1)
-      bool q2_brick = false;
-    };
-    std::vector<std::unique_ptr<Taps>> taps;
-    // general hierarchies (gls_mg_attach_transfers): per level pair the prolongation P (fine rows), the
-    // restriction R = P^T (coarse rows) as CSR, and the state injection (coarse DoF <- fine DoF)
-    bool csr = false;
-    bool ilu_smooth = false;  // gls_mg_params.smoother = 1: ILU(0) sweeps on the levels above the coarsest
-    struct Csr {
-      DevBuf<int64_t> poff, roff;
-      DevBuf<int32_t> pcol, rcol, inj;
-      DevBuf<double> pw, rw;
-      int64_t nf = 0, nc = 0;
-      int plane = 1, rlane = 1;  // SpMV lanes per row (from the mean row length)
-    };
-    std::vector<std::unique_ptr<Csr>> xfer;
-    std::vector<gls_ctx *> ilu_levels;  // levels whose ILU(0) smoother this attach created (smoother = 1)
-    DevBuf<double> xwork;  // two-pass transfer intermediate (coarse xy x fine z, 4 fields)
-    // coarsest level: direct solve with the probed, regularised, inverted Jacobian
-    bool direct = false, direct_ok = false;
-    // per-cell coarsest level: its matrix for the direct solve assembled by the ILU's colored batched probes
-    // (a structure-only ILU(0) on that level, never factored) instead of one J.v per column
-    gls_ctx *probe_ilu = nullptr;
-    DevBuf<int32_t> pinv;
-    // direct solve by LU (rocSOLVER getrf + getri -> explicit inverse, applied by rocBLAS gemv) with
-    // the first pressure DoF pinned (enclosed-flow gauge); falls back to the one-workgroup
-    // Gauss-Jordan (mg_dense_invert) for small levels or when the LU reports a zero pivot
-    bool lu = false;
-    // large coarsest levels (kDirectSmall < n <= kDirectMax, e.g. a Q1-Q1 p-level of a 4.7 k-cell base mesh):
-    // the pinned FP64 matrix rounded to FP32, pivoted sgetrf + sgetri, applied by sgemv (a preconditioner's
-    // coarse solve: FP32 rounding of A^-1 is far below the V-cycle's own error; half the bytes and the FP32
-    // matrix-core rate for the O(n^3) setup)
-    bool lu32 = false;
-    bool lu32_npvt = false;  // the FP32 factor is unpivoted (applied by dense_lu_solve_f32), else an explicit inverse
-    bool lu32_refine = false;  // ... applied with one step of iterative refinement against the FP64 matrix
-    // banded coarse matrix: the probed CSR's Cuthill-McKee order kept (the dense array holds A in that order), its
-    // lower / upper bandwidths; the factorization works by column blocks as wide as the band (no fill outside it
-    // without pivoting) and the solves skip the blocks outside it. configs[4]'s 25 k-DoF Q1-Q1 p-level: ~1.9 k
-    bool lu_cm = false;
-    int64_t lu_bl = -1, lu_bu = -1, lu_pin_cm = -1;
-    DevBuf<int32_t> lu_ident;  // identity permutation (csr_to_dense in the CSR's own order)
-    DevBuf<double> lu_tmp;     // the coarse right-hand side / correction in that order
-    DevBuf<float> probe32, b32, x32;
-    DevBuf<double> chk32;    // the FP32 factor's check: A x - b for b = 1 (FP64)
-    int64_t npvt_ipiv_n = -1;  // ipiv holds the identity permutation of this size (unpivoted LU)
-    struct Blas {  // owning rocBLAS handle (movable, destroyed with the MG state)
-      rocblas_handle h = nullptr;
-      Blas() = default;
-      Blas(const Blas &) = delete;
-      Blas &operator=(const Blas &) = delete;
-      Blas(Blas &&o) noexcept : h(o.h) { o.h = nullptr; }
-      Blas &operator=(Blas &&o) noexcept {
-        if (this != &o) {
-          if (h) rocblas_destroy_handle(h);
-          h = o.h;
-          o.h = nullptr;
-        }
-        return *this;
-      }
-      ~Blas() {
-        if (h) rocblas_destroy_handle(h);
-      }
-      operator rocblas_handle() const { return h; }
-    } blas;
-    DevBuf<int> ipiv, info;
-    DevBuf<double> probe, aug, unit;
-    DevBuf<double> probe_bak;  // the probed coarse matrix kept for the pivoted retry of an unpivoted LU
-    DevBuf<double> chk;        // coarse_inverse_check's y = A^-1 e and z = A y
-    DevBuf<int> status;
-    // the FP32 unpivoted factorization and its check run on a stream of their own, overlapping the finer levels'
-    // ILU setup and first smoothing on the context stream; the first coarse solve waits for them
-    // (coarse_lu32_finish). Declared after the buffers it uses, so it is destroyed (synchronized) first.
-    // rocSOLVER's getrf returns to the host only when the factorization is done (82-89 ms of host time at
-    // n = 25000, box r06v), so the calls are made from a worker thread: the host thread queues the finer levels'
-    // setup meanwhile
-    struct Side {
-      hipStream_t s = nullptr;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      std::thread worker;
-      int rc = 0;  // the worker's result: 0, or the failing call's number
-      Side() = default;
-      Side(const Side &) = delete;
-      Side &operator=(const Side &) = delete;
-      Side(Side &&o) noexcept : s(o.s), e0(o.e0), e1(o.e1), worker(std::move(o.worker)), rc(o.rc) {
-        o.s = nullptr, o.e0 = o.e1 = nullptr;
-      }
-      Side &operator=(Side &&o) noexcept {
-        if (this != &o) {
-          reset();
-          s = o.s, e0 = o.e0, e1 = o.e1, worker = std::move(o.worker), rc = o.rc;
-          o.s = nullptr, o.e0 = o.e1 = nullptr;
-        }
-        return *this;
-      }
-      void join() {
-        if (worker.joinable()) worker.join();
-      }
-      hipError_t ensure() {
-        if (s) return hipSuccess;
-        hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&e0, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&e1, hipEventDisableTiming);
-        return e;
-      }
-      void reset() {
-        join();
-        if (s) {
-          (void)hipStreamSynchronize(s);
-          (void)hipStreamDestroy(s);
-        }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        s = nullptr, e0 = e1 = nullptr;
-      }
-      ~Side() { reset(); }
-    } side;
-    bool lu_pending = false;  // side-stream factorization in flight, not yet checked
-    int64_t lu_n = 0, lu_pin = 0;
-    DevBuf<double> lu_rel;  // |A x - 1| of the check (device pointer mode)
-    // coarsest-level Jacobi sweeps (single rank, fused brick path) replayed as one HIP graph: the
-    // ~2×csweeps tiny launches per V-cycle are captured once per state (mg_prepare) and launched
-    // as a single graph by every V-cycle of that Newton step
-    struct Graph {
-      hipGraphExec_t h = nullptr;
-      Graph() = default;
-      Graph(const Graph &) = delete;
-      Graph &operator=(const Graph &) = delete;
-      Graph(Graph &&o) noexcept : h(o.h) { o.h = nullptr; }
-      Graph &operator=(Graph &&o) noexcept {
-        if (this != &o) {
-          reset();
-          h = o.h;
-          o.h = nullptr;
-        }
-        return *this;
-      }
-      void reset() {
-        if (h) (void)hipGraphExecDestroy(h);
-        h = nullptr;
-      }
-      ~Graph() { reset(); }
-    } cgraph;
-    std::vector<unsigned char> cgraph_key;  // launch parameters the graph was captured with
-    bool cgraph_failed = false;  // capture refused once: stay on plain launches
-    bool dirty = true;
-    // multi-GPU (gls_mg_set_coarse_replica): the coarsest DISTRIBUTED level's correction is computed
-    // by a replica -- a single-rank context of that level's whole mesh with its own hierarchy below
-    // it -- identically on every rank, from the all-reduced (gathered) right-hand side
-    gls_ctx *replica = nullptr;
-    // general hierarchies across ranks (gls_mg_attach_replica): the distributed fine level smooths its own
-    // rows, every coarser level is a replica on every rank (rep2, with its own hierarchy); restriction over the
-    // rank's OWNED fine rows into the replica numbering + a sum all-reduce, prolongation onto all local rows
-    bool rep_csr = false;
-    gls_ctx *rep2 = nullptr;
-    DevBuf<int64_t> r2p_off, r2r_off;  // P (local fine rows x replica DoFs), R = P_owned^T (replica rows)
-    DevBuf<int32_t> r2p_col, r2r_col;
-    DevBuf<double> r2p_w, r2r_w;
-    int r2p_lane = 1, r2r_lane = 1;
-    DevBuf<int32_t> r2inj_c, r2inj_f;  // replica DoF <- owned local fine DoF (state injection pairs)
-    DevBuf<int32_t> rep_own_loc, rep_own_glob;  // owned local rows of the coarsest level -> replica rows
-    DevBuf<int32_t> rep_map;                    // every local row -> replica row
-    DevBuf<double> rep_b, rep_x, rep_tmp, rep_u[4];
-  } mg;
-  double time_steps[4] = {1, 1, 1, 1};
-  // frozen Jacobian (skip_newton: the matrix and its preconditioner are reused across Newton
-  // iterations, skip_newton_non_linear_solver.h:66-70, 126-130): snapshot of the state and time
-  // coefficients the Jacobian operators (J.v, diagonal, linearization, multigrid levels) are taken
-  // at, while gls_set_state / gls_set_time move only the residual's state
-  struct JacFreeze {
-    bool on = false;
-    DevBuf<double> u, h[3];
-    bool has[3] = {false, false, false};
-    double alpha[4] = {0, 0, 0, 0}, alpha_jac = 0., sdt2 = 0., ts[4] = {1, 1, 1, 1};
-    int n_hist = 0, scheme = GLS_STEADY;
-  } jf;
-  int skip_consecutive = 0;  // SkipNewtonNonLinearSolver::consecutive_iters (persists across solves)
-  bool probe_local = false;  // ILU probe across ranks: J.v on the rank's cells only (no ghost exchange)
-  // TimerOutput sections of the reference's Newton/GMRES path (gls_section_timing): wall seconds and
-  // calls, stream-synchronised at the section boundaries while enabled
-  bool sec_on = false;
-  double sec_t[GLS_N_SECTIONS] = {};
-  int sec_n[GLS_N_SECTIONS] = {};
-  // timing
-  bool timing = false;
-  struct Ev { int which; hipEvent_t a, b; };
-  std::vector<Ev> events;
-  // residual, J.v, diagonal, J.v linearization, FP32 smoother J.v, brick-surface slab sums
-  double t_ms[6] = {0, 0, 0, 0, 0, 0};
-  int64_t t_n[6] = {0, 0, 0, 0, 0, 0};
-
-  ~gls_ctx() {
-    if (hpin) (void)hipHostFree(hpin);
-    for (auto &e : events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    if (dist.ev_ready) (void)hipEventDestroy(dist.ev_ready);
-    if (dist.ev_done) (void)hipEventDestroy(dist.ev_done);
-    if (dist.xstream) (void)hipStreamDestroy(dist.xstream);
-    if (own_stream && stream) (void)hipStreamDestroy(stream);
-  }
-};
 
 namespace {
 
@@ -955,6 +487,8 @@ void mapped_geometry(int dim, int md, int nq1d, const double *S, double *out) {
   }
 }
 
+}  // namespace
+namespace gls_impl {  // declared in gls_ctx.hpp
 // cell->measure() of a mapped cell from its corner support points (exact bilinear / trilinear
 // volume: 2-point Gauss of the multilinear det J)
 double corner_measure(int dim, int md, const double *S) {
@@ -984,13 +518,8 @@ double corner_measure(int dim, int md, const double *S) {
   return vol;
 }
 
-int check_ctx(gls_ctx *c) {
-  if (!c) return set_err(GLS_EINVAL, "null context");
-  return GLS_OK;
-}
-
 // jac: parameters of the Jacobian operators (the frozen snapshot when gls_freeze_jacobian is on)
-gls::OpParams make_params(gls_ctx *c, bool jac = false) {
+gls::OpParams make_params(gls_ctx *c, bool jac) {
   gls::OpParams P;
   std::memset(&P, 0, sizeof(P));
   P.n_cells = c->n_cells;
@@ -1027,25 +556,8 @@ gls::OpParams make_params(gls_ctx *c, bool jac = false) {
   }
   return P;
 }
-
-struct TimedLaunch {
-  gls_ctx *c;
-  int which;
-  hipEvent_t a = nullptr, b = nullptr;
-  TimedLaunch(gls_ctx *c_, int w) : c(c_), which(w) {
-    if (c->timing) {
-      (void)hipEventCreate(&a);
-      (void)hipEventCreate(&b);
-      (void)hipEventRecord(a, c->stream);
-    }
-  }
-  ~TimedLaunch() {
-    if (c->timing) {
-      (void)hipEventRecord(b, c->stream);
-      c->events.push_back({which, a, b});
-    }
-  }
-};
+}  // namespace gls_impl
+namespace {
 
 // ---- distributed hooks (no-ops on a single rank)
 int dist_import(gls_ctx *c, double *x) {
@@ -1165,7 +677,6 @@ hipError_t slab_sum(gls_ctx *c, double *y) {
                              c->n_vnodes, y, c->stream);
 }
 
-int rccl_exchange_on(gls_ctx *c, int phase, hipStream_t stream);  // RCCL transport (below)
 
 // the brick split: a brick is a boundary brick when one of its cells holds a flagged node (ghost or
 // exported); boundary bricks first, then interior ones, each in ascending (Morton) order
@@ -1209,6 +720,8 @@ bool split_jv_enabled(gls_ctx *c) {
   return true;
 }
 
+}  // namespace
+namespace gls_impl {  // declared in gls_ctx.hpp
 // slots of every node in the per-cell element vectors [n_cells][NV*dim + NP], ascending (cell, local
 // node) order: the fixed summation order of gather_element_vectors
 int ensure_element_maps(gls_ctx *c) {
@@ -1238,16 +751,8 @@ int ensure_element_maps(gls_ctx *c) {
   GLS_TRY(c->ev_pslot.upload(pslot.data(), std::max<size_t>(pslot.size(), 1)));
   return c->ev.alloc((size_t)c->n_cells * el);
 }
-
-int ensure_diag(gls_ctx *c);
-// the per-cell linearization cache: on for contexts that run the per-cell kernels
-bool cell_cache_on(const gls_ctx *c) {
-  return !c->use_brick && c->n_cells > 0;
-}
-size_t cell_cache_size(const gls_ctx *c) {
-  const int dim = c->dim;
-  return (size_t)c->n_cells * (size_t)gls::ipow(c->nq1d, dim) * (size_t)(dim + dim * dim + 1 + dim);
-}
+}  // namespace gls_impl
+namespace {
 
 // adapted forest bricks: the pencil linearization (no output) at the current state
 int oct_lin(gls_ctx *c) {
@@ -1420,6 +925,8 @@ int run_cell(gls_ctx *c, int mode, const double *v, double *y) {
   return GLS_OK;
 }
 
+}  // namespace
+namespace gls_impl {  // declared in gls_ctx.hpp
 int ensure_diag(gls_ctx *c) {
   if (c->diag_valid) return GLS_OK;
   GLS_TRY(run_cell(c, gls::MODE_DIAG, nullptr, c->diag.p));
@@ -1431,6 +938,8 @@ int ensure_diag(gls_ctx *c) {
   c->diag_valid = true;
   return GLS_OK;
 }
+}  // namespace gls_impl
+namespace {
 
 int device_dot(gls_ctx *c, const double *a, const double *b, double *host_out) {
   return dist_multidot(c, a, 0, 1, b, host_out);
@@ -2040,11 +1549,6 @@ int smoother_apply(gls_ctx *g, const double *v, double *y, const double *rb = nu
 // pxc != nullptr (only where mg_fused_prolong_ok): the sweep starts from x + P pxc, the coarse correction of the
 // next-coarser nested level interpolated in the J.v's gather; y (scratch) carries x + P pxc of the brick-surface
 // nodes from the J.v to the slab sum.
-}  // namespace
-static int ensure_ilu(gls_ctx *c);
-static int ilu_probe(gls_ctx *c);
-static int apply_ilu(gls_ctx *c, const double *v, double *z);
-namespace {
 // one ILU(0) smoothing sweep x <- x + M^-1 (b - A x) (M = the level's ILU(0), undamped; z: scratch)
 int ilu_sweep(gls_ctx *g, double *x, const double *b, double *y, double *z) {
   GLS_TRY(ensure_ilu(g));
@@ -3198,223 +2702,6 @@ int mg_vcycle(gls_ctx *c, int l, const double *b, double *x) {
   return GLS_OK;
 }
 
-#define RS_TRY(x)                                                                        \
-  do {                                                                                   \
-    const rocsparse_status rs_ = (x);                                                    \
-    if (rs_ != rocsparse_status_success) return set_err(GLS_EHIP, "%s: rocsparse status %d", #x, (int)rs_); \
-  } while (0)
-
-// assembled ILU(0): probe the operator into the CSR values (one J.v per color and DoF slot), perturb
-// the diagonal, factor in place; once per Jacobian state (invalidated with the diagonal)
-// the per-cell path on one rank: all probes in batches of B vectors, each step one launch over the batch
-// (unit vectors, hanging-line values, the per-cell J.v with zero cell batches skipped, the ordered
-// element-vector sums, condensation, constrained rows, extraction) -- the same operations per probe as
-// gls_jacobian_apply, without one launch sequence per probe
-static int ilu_probe_batched(gls_ctx *c) {
-  auto &I = c->ilu;
-  const int64_t n = c->n_dofs;
-  hipStream_t s = c->stream;
-  if (!c->u) return set_err(GLS_EINVAL, "gls_set_state was not called");
-  GLS_TRY(ensure_element_maps(c));
-  if (c->con_dofs.n) GLS_TRY(ensure_diag(c));
-  const int dim = c->dim, nv = gls::ipow(c->k + 1, dim), np = gls::ipow(c->kp + 1, dim);
-  const int64_t el = (int64_t)nv * dim + np, evs = (int64_t)c->n_cells * el;
-  const char *bs = std::getenv("GLS_ILU_PROBE_BATCH");
-  const int64_t budget = (int64_t)1 << 31;  // bytes of V, C V, Y and the element vectors per batch
-  int B = bs ? std::atoi(bs) : (int)std::min<int64_t>(I.n_probes, std::max<int64_t>(1, budget / (8 * (3 * n + evs))));
-  B = std::max(1, std::min(B, I.n_probes));
-  if (I.bV.n < (size_t)B * n) {
-    GLS_TRY(I.bV.alloc((size_t)B * n));
-    GLS_TRY(I.bY.alloc((size_t)B * n));
-  }
-  if (c->hang.on && I.bC.n < (size_t)B * n) GLS_TRY(I.bC.alloc((size_t)B * n));
-  if (c->bev.n < (size_t)B * evs) GLS_TRY(c->bev.alloc((size_t)B * evs));
-  const int cb = gls::cell_kernel_cells_per_block(dim, c->k, c->nq1d, true), nblk = (c->n_cells + cb - 1) / cb;
-  if (c->bact.n < (size_t)B * nblk) GLS_TRY(c->bact.alloc((size_t)B * nblk));
-  if (I.fill > 0) HIP_TRY(gls::vec_fill(I.val.p, I.nnz, 0.0, s));  // fill-in positions start at 0
-  // recorded activity (GLS_ILU_PROBE_LIST=0: every (probe, batch) block tests its vector, every time)
-  const char *wl_env = std::getenv("GLS_ILU_PROBE_LIST");
-  const bool wl_on = !(wl_env && wl_env[0] == '0');
-  const bool use_list = wl_on && !I.woff.empty() && I.wB == B && I.wnblk == nblk;
-  const bool record = wl_on && !use_list;
-  // listed blocks read u, grad u, tau and R_s from the linearization cache of this state (the diagonal pass writes
-  // it for every cell; not on forests, whose cache covers the cells outside the bricks only)
-  bool cq_probe = use_list && cell_cache_on(c) && !c->oct.on;
-  if (cq_probe) {
-    GLS_TRY(ensure_diag(c));
-    cq_probe = c->cq_valid && c->cq.n == cell_cache_size(c);
-  }
-  std::vector<int32_t> hlist;
-  std::vector<int64_t> hoff;
-  std::vector<uint8_t> hact;
-  if (record) {
-    GLS_TRY(I.wact.alloc((size_t)I.n_probes * nblk));
-    hoff.push_back(0);
-  }
-  for (int p0 = 0; p0 < I.n_probes; p0 += B) {
-    const int nb = std::min(B, I.n_probes - p0);
-    HIP_TRY(gls::vec_fill(I.bV.p, (int64_t)nb * n, 0.0, s));
-    const int64_t d0 = I.pdoff[(size_t)p0], d1 = I.pdoff[(size_t)(p0 + nb)];
-    HIP_TRY(gls::probe_set_batched(I.bV.p, n, I.pdofs.p + d0, I.pdpid.p + d0, p0, d1 - d0, s));
-    const double *Cv = I.bV.p;
-    if (c->hang.on) {  // C v (hanging entries interpolated from their masters) in a copy: the constrained
-      // rows below take the probe vector itself, as gls_jacobian_apply does
-      HIP_TRY(gls::vec_copy(I.bC.p, I.bV.p, (int64_t)nb * n, s));
-      HIP_TRY(gls::vec_csr_gather_set_b(I.bC.p, c->hang.dof.p, c->hang.ooff.p, c->hang.omaster.p, c->hang.ow.p,
-                                        (int64_t)c->hang.dof.n, nb, n, s));
-      Cv = I.bC.p;
-    }
-    gls::OpParams P = make_params(c, true);
-    P.v = Cv;
-    P.y = I.bY.p;
-    P.hmask = c->hang.on ? c->hang.hmask.p : nullptr;
-    P.ev = c->bev.p;
-    // (the first, recording run re-derives the linearization in every (probe, cell batch) block: with all blocks
-    // launched, reading the cache moved more bytes than the state gathers -- configs[4]'s ILU setup ran 1.4 ms per
-    // Newton step slower; the listed runs read it, profiles/r05_ab_probe_cache.txt)
-    P.bv_stride = n;
-    P.bev_stride = evs;
-    P.n_probe = nb;
-    const int chunk = p0 / B;
-    P.bact = use_list ? I.wact.p + (size_t)p0 * nblk : c->bact.p;
-    if (use_list) {
-      P.work = I.wlist.p + 2 * I.woff[(size_t)chunk];
-      P.n_work = (int)(I.woff[(size_t)chunk + 1] - I.woff[(size_t)chunk]);
-      if (cq_probe) {
-        P.cq = c->cq.p;
-        P.cq_mode = 2;
-      }
-    }
-    if (!use_list || P.n_work > 0) {
-      TimedLaunch t(c, (int)gls::MODE_JV);
-      HIP_TRY(gls::launch_cell_kernel(c->dim, c->k, c->kp, c->nq1d, gls::MODE_JV, P, c->tables, s));
-    }
-    if (record) {  // this chunk's flags: kept on the device for the gathers, listed on the host
-      HIP_TRY(hipMemcpyAsync(I.wact.p + (size_t)p0 * nblk, c->bact.p, (size_t)nb * nblk, hipMemcpyDeviceToDevice, s));
-      hact.resize((size_t)nb * nblk);
-      HIP_TRY(hipMemcpyAsync(hact.data(), c->bact.p, hact.size(), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      for (int v = 0; v < nb; ++v)
-        for (int64_t b = 0; b < nblk; ++b)
-          if (hact[(size_t)v * nblk + b]) {
-            hlist.push_back(v);
-            hlist.push_back((int32_t)b);
-          }
-      hoff.push_back((int64_t)hlist.size() / 2);
-    }
-    HIP_TRY(gls::gather_element_vectors_b(I.bY.p, c->bev.p, c->ev_voff.p, c->ev_vslot.p, c->n_vnodes, c->ev_poff.p,
-                                          c->ev_pslot.p, c->n_pnodes, c->dim, nb, n, evs, P.bact, el, cb, nblk, s));
-    if (c->hang.on)
-      HIP_TRY(gls::vec_csr_condense_b(I.bY.p, c->hang.tm.p, c->hang.toff.p, c->hang.tdof.p, c->hang.tw.p,
-                                      (int64_t)c->hang.tm.n, nb, n, s));
-    HIP_TRY(gls::vec_gather_scale_set_b(I.bY.p, c->diag.p, I.bV.p, c->con_dofs.p, (int64_t)c->con_dofs.n, nb, n, s));
-    const int64_t e0 = I.peoff[(size_t)p0], e1 = I.peoff[(size_t)(p0 + nb)];
-    HIP_TRY(gls::probe_extract_batched(I.val.p, I.pent.p + e0, I.prow.p + e0, I.pepid.p + e0, p0, e1 - e0, I.bY.p, n, s));
-  }
-  if (I.ghost_diag.n) HIP_TRY(gls::vec_set_const_indexed64(I.val.p, I.ghost_diag.p, (int64_t)I.ghost_diag.n, 1.0, s));
-  if (record) {
-    GLS_TRY(I.wlist.upload(hlist.data(), hlist.size()));
-    I.woff.swap(hoff);
-    I.wB = B;
-    I.wnblk = nblk;
-  }
-  return GLS_OK;
-}
-
-static int ilu_probe(gls_ctx *c) {  // I.val <- the operator's CSR values (gls_jacobian_apply)
-  auto &I = c->ilu;
-  const int64_t n = c->n_dofs;
-  hipStream_t s = c->stream;
-  if (!c->dist.on && !c->use_brick && !std::getenv("GLS_ILU_PROBE_LOOP")) return ilu_probe_batched(c);
-  if (I.fill > 0 || c->dist.on) HIP_TRY(gls::vec_fill(I.val.p, I.nnz, 0.0, s));  // fill-in positions start at 0
-  // across ranks the constrained rows' diagonal is the exchanged one: computed before the local probes
-  if (c->dist.on && (c->con_dofs.n || I.complete)) GLS_TRY(ensure_diag(c));
-  c->probe_local = c->dist.on;  // the probe's J.v: the rank's cells only, no ghost exchange
-  struct ProbeLocalGuard {      // every exit path (errors included) restores the exchanging operator
-    gls_ctx *c;
-    ~ProbeLocalGuard() { c->probe_local = false; }
-  } guard{c};
-  auto &D = c->dist;
-  const int rounds = I.complete ? I.n_rounds : I.n_probes;
-  for (int p = 0; p < rounds; ++p) {
-    if (p < I.n_probes) {
-      HIP_TRY(gls::vec_fill(I.vbuf.p, n, 0.0, s));
-      HIP_TRY(gls::vec_set_const_indexed(I.vbuf.p, I.pdofs.p + I.pdoff[(size_t)p],
-                                         I.pdoff[(size_t)p + 1] - I.pdoff[(size_t)p], 1.0, s));
-      GLS_TRY(gls_jacobian_apply(c, I.vbuf.p, I.ybuf.p));
-      HIP_TRY(gls::csr_probe_extract(I.val.p, I.pent.p + I.peoff[(size_t)p], I.prow.p + I.peoff[(size_t)p],
-                                     I.peoff[(size_t)p + 1] - I.peoff[(size_t)p], I.ybuf.p, s, c->dist.on));
-    }
-    if (!I.complete) continue;
-    // ghost rows of this probe (the local cells' part of a neighbour's owned rows) to their owners
-    if (p < I.n_probes) HIP_TRY(gls::vec_pack_dofs(I.ybuf.p, D.recv_nodes.p, D.n_recv, D.recv_buf, s));
-    else if (D.n_recv) HIP_TRY(gls::vec_fill(D.recv_buf, D.n_recv, 0.0, s));
-    if (D.xchg(D.user, 1) != 0) return set_err(GLS_ECOMM, "ILU probe exchange failed");
-    const int64_t a = I.rr[(size_t)p], b = I.rr[(size_t)p + 1];
-    if (b > a) HIP_TRY(gls::vec_add_pos_ordered(I.val.p, I.ru.p + a, I.ruoff.p + a, I.rslot.p, b - a, D.send_buf, s));
-  }
-  c->probe_local = false;
-  if (I.ghost_diag.n) HIP_TRY(gls::vec_set_const_indexed64(I.val.p, I.ghost_diag.p, (int64_t)I.ghost_diag.n, 1.0, s));
-  return GLS_OK;
-}
-static int apply_ilu(gls_ctx *c, const double *v, double *z);
-static int ensure_ilu(gls_ctx *c) {
-  auto &I = c->ilu;
-  if (!I.on || I.valid) return GLS_OK;
-  const int64_t n = c->n_dofs;
-  hipStream_t s = c->stream;
-  const bool verbose = std::getenv("GLS_ILU_VERBOSE") != nullptr;
-  auto now = [&]() {
-    if (verbose) (void)hipStreamSynchronize(s);
-    return std::chrono::steady_clock::now();
-  };
-  const auto t0 = now();
-  GLS_TRY(ilu_probe(c));
-  HIP_TRY(gls::csr_diag_perturb(I.val.p, I.didx.p, n, I.athresh, I.rthresh, s));
-  const auto t1 = now();
-  const rocsparse_int m = (rocsparse_int)n, nnz = (rocsparse_int)I.nnz;
-  if (I.h) RS_TRY(rocsparse_set_stream(I.h, s));  // (no handle past 2^31 entries: multicolor kernels only)
-  if (I.mc_factor)
-    HIP_TRY(gls::ilu_mc_factor(I.mc_grow.p, I.mc_cg.data(), (int)I.mc_cg.size() - 1, I.rowp.p, I.col.p, I.val.p,
-                               I.mc_lsp.p, I.didx.p, I.boost_tol, I.boost_val, I.mc_moff.p,
-                               I.mc_map.n ? I.mc_map.p : nullptr, I.mc_compact, I.rdiag.p, s));
-  else
-    RS_TRY(rocsparse_dcsrilu0(I.h, m, nnz, I.dA, I.val.p, I.rowp32.p, I.col.p, I.info, rocsparse_solve_policy_auto, I.work.p));
-  I.valid = true;
-  if (verbose) {
-    const auto t2 = now();
-    rocsparse_int zp = -1;
-    const rocsparse_status st = I.h ? rocsparse_csrilu0_zero_pivot(I.h, I.info, &zp) : rocsparse_status_success;
-    GLS_TRY(apply_ilu(c, I.ybuf.p, I.ybuf.p == nullptr ? nullptr : c->tmp1.p ? c->tmp1.p : I.ybuf.p));
-    const auto t3 = now();
-    std::printf("ilu: %d probes %.2f ms, csrilu0 %.2f ms (zero pivot status %d at %d), one apply %.3f ms\n", I.n_probes,
-                std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                std::chrono::duration<double, std::milli>(t2 - t1).count(), (int)st, (int)zp,
-                std::chrono::duration<double, std::milli>(t3 - t2).count());
-  }
-  return GLS_OK;
-}
-static int apply_ilu(gls_ctx *c, const double *v, double *z) {
-  auto &I = c->ilu;
-  const rocsparse_int m = (rocsparse_int)c->n_dofs, nnz = (rocsparse_int)I.nnz;
-  const double one = 1.0;
-  if (I.h) RS_TRY(rocsparse_set_stream(I.h, c->stream));
-  // z = P^T U^-1 L^-1 P v (P: the Cuthill-McKee renumbering the factors live in)
-  HIP_TRY(gls::vec_permute(I.vbuf.p, v, I.perm.p, c->n_dofs, 0, c->stream));
-  if (I.mc_solve) {  // multicolor order: color-by-color solves (gls_ilu_kernels.hip)
-    HIP_TRY(gls::ilu_mc_solve(I.mc_desc.p, I.mc_cg.data(), (int)I.mc_cg.size() - 1, I.col.p, I.val.p, I.vbuf.p,
-                              I.tbuf.p, I.vbuf.p, I.mc_wl.data(), I.mc_wu.data(), c->stream));
-    HIP_TRY(gls::vec_permute(z, I.vbuf.p, I.perm.p, c->n_dofs, 1, c->stream));
-    return GLS_OK;
-  }
-  RS_TRY(rocsparse_dcsrsv_solve(I.h, rocsparse_operation_none, m, nnz, &one, I.dL, I.val.p, I.rowp32.p, I.col.p, I.info,
-                                I.vbuf.p, I.tbuf.p, rocsparse_solve_policy_auto, I.work.p));
-  RS_TRY(rocsparse_dcsrsv_solve(I.h, rocsparse_operation_none, m, nnz, &one, I.dU, I.val.p, I.rowp32.p, I.col.p, I.info,
-                                I.tbuf.p, I.vbuf.p, rocsparse_solve_policy_auto, I.work.p));
-  HIP_TRY(gls::vec_permute(z, I.vbuf.p, I.perm.p, c->n_dofs, 1, c->stream));
-  return GLS_OK;
-}
-
 // z = M^{-1} v : Jacobi, assembled ILU(0) or a multigrid V-cycle when attached
 int apply_prec(gls_ctx *c, const double *v, double *z) {
   if (c->mg.on && c->mg.rep_csr) return mg_vcycle_rep2(c, v, z);
@@ -3489,460 +2776,6 @@ int gls_mg_prolong_smooth(gls_ctx *c, int level, const double *xc, double *x, co
   return smoother_sweep(g, x, b, y, omega, zs);
 }
 
-// --------------------------------------------------------------------------------------------
-// Kelly error indicator (navier_stokes_base.cc:612-652)
-// --------------------------------------------------------------------------------------------
-namespace {
-// face neighbours of a conforming mesh: faces match by their vertex node ids (periodic wraps share
-// node ids, so a wrapped face has its periodic neighbour)
-int build_face_neighbours(gls_ctx *c) {
-  const int dim = c->dim, k = c->k, nv = gls::ipow(k + 1, dim);
-  std::vector<int32_t> cn((size_t)c->n_cells * nv);
-  if (!cn.empty() && hipMemcpy(cn.data(), c->cell_vnodes.p, cn.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-    return set_err(GLS_EHIP, "cell map download failed");
-  std::map<std::array<int32_t, 4>, std::pair<int, int>> open;  // face key -> (cell, face slot)
-  std::vector<int32_t> nbr((size_t)c->n_cells * 2 * dim, -1);
-  for (int cell = 0; cell < c->n_cells; ++cell)
-    for (int d = 0; d < dim; ++d)
-      for (int sd = 0; sd < 2; ++sd) {
-        std::array<int32_t, 4> key = {-1, -1, -1, -1};
-        int nk = 0;
-        for (int v = 0; v < (1 << dim); ++v) {  // cell vertices with coordinate d on side sd
-          if (((v >> d) & 1) != sd) continue;
-          int a = 0, st = 1;
-          for (int e = 0; e < dim; ++e, st *= k + 1) a += ((v >> e) & 1) * k * st;
-          key[nk++] = cn[(size_t)cell * nv + a];
-        }
-        std::sort(key.begin(), key.begin() + nk);
-        auto it = open.find(key);
-        if (it == open.end()) {
-          open.emplace(key, std::make_pair(cell, 2 * d + sd));
-        } else {
-          nbr[(size_t)cell * 2 * dim + 2 * d + sd] = it->second.first;
-          nbr[(size_t)it->second.first * 2 * dim + it->second.second] = cell;
-          open.erase(it);
-        }
-      }
-  return c->face_nbr.upload(nbr.data(), nbr.size());
-}
-
-gls::KellyTables kelly_tables(int m, int nq) {
-  gls::KellyTables T;
-  std::memset(&T, 0, sizeof(T));
-  double xq[gls::kMaxQ1D], wq[gls::kMaxQ1D], xn[gls::kMaxNodes1D];
-  gauss_points(nq, xq, wq);
-  lobatto_points(m, xn);
-  T.nq = nq;
-  for (int a = 0; a <= m; ++a) {
-    double v, dd, s2;
-    for (int q = 0; q < nq; ++q) {
-      lagrange_1d(m, xn, a, xq[q], v, dd, s2);
-      T.V[q][a] = v;
-    }
-    lagrange_1d(m, xn, a, 0.0, v, dd, s2);
-    T.De[0][a] = dd;
-    lagrange_1d(m, xn, a, 1.0, v, dd, s2);
-    T.De[1][a] = dd;
-  }
-  for (int q = 0; q < nq; ++q) {
-    T.w[q] = wq[q];
-    T.xq[q] = xq[q];
-  }
-  for (int a = 0; a <= m; ++a) T.xn[a] = xn[a];
-  return T;
-}
-}  // namespace
-
-int gls_kelly_estimate(gls_ctx *c, const double *sol, int variable, double *eta) {
-  GLS_TRY(check_ctx(c));
-  if (!sol || !eta || (variable != 0 && variable != 1)) return set_err(GLS_EINVAL, "gls_kelly_estimate: bad arguments");
-  if (c->hang.on) return set_err(GLS_EINVAL, "gls_kelly_estimate: conforming meshes only (no hanging nodes)");
-  if (c->map_degree > 0) return set_err(GLS_EINVAL, "gls_kelly_estimate: axis-aligned box cells only");
-  if (c->nq1d + 1 > gls::kMaxQ1D) return set_err(GLS_EINVAL, "gls_kelly_estimate: face rule too large");
-  if (!c->face_nbr.p && c->n_cells > 0) GLS_TRY(build_face_neighbours(c));
-  const bool pres = variable == 1;
-  const int m = pres ? c->kp : c->k;
-  const int32_t *nodes = pres && c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;
-  const gls::KellyTables T = kelly_tables(m, c->nq1d + 1);  // QGauss<dim-1>(n_q + 1)
-  HIP_TRY(gls::launch_kelly(c->dim, m, nodes, c->face_nbr.p, c->geo.p, sol, c->n_cells, pres ? 1 : c->dim,
-                            pres ? (int64_t)c->dim * c->n_vnodes : 0, pres ? 1 : c->dim, T, eta, c->stream));
-  return GLS_OK;
-}
-
-// Kelly indicator on meshes with hanging faces (gls_octree_faces lists the face pieces): the face
-// integrals on the device, then eta_K = sqrt(diam(K)/24 * sum of K's pieces) in a fixed order
-int gls_kelly_estimate_faces(gls_ctx *c, const double *sol, int variable, int64_t n_faces, const int32_t *fa,
-                             const int32_t *fb, const int32_t *fdir, const double *rect_a, const double *rect_b,
-                             double *eta) {
-  GLS_TRY(check_ctx(c));
-  if (!sol || !eta || (variable != 0 && variable != 1) || n_faces < 0 || (n_faces > 0 && (!fa || !fb || !fdir || !rect_a || !rect_b)))
-    return set_err(GLS_EINVAL, "gls_kelly_estimate_faces: bad arguments");
-  if (c->map_degree > 0) return set_err(GLS_EINVAL, "gls_kelly_estimate_faces: axis-aligned box cells only");
-  for (int64_t e = 0; e < n_faces; ++e)
-    if (fa[e] < 0 || fa[e] >= c->n_cells || fb[e] < 0 || fb[e] >= c->n_cells || fdir[e] < 0 || fdir[e] >= c->dim)
-      return set_err(GLS_EINVAL, "gls_kelly_estimate_faces: face %lld out of range", (long long)e);
-  const bool pres = variable == 1;
-  const int m = pres ? c->kp : c->k;
-  const int32_t *nodes = pres && c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;
-  const gls::KellyTables T = kelly_tables(m, c->nq1d + 1);  // QGauss<dim-1>(n_q + 1) on every piece
-  DevBuf<int32_t> dfa, dfb, dfd;
-  DevBuf<double> dra, drb, dfi;
-  GLS_TRY(dfa.upload(fa, (size_t)n_faces));
-  GLS_TRY(dfb.upload(fb, (size_t)n_faces));
-  GLS_TRY(dfd.upload(fdir, (size_t)n_faces));
-  GLS_TRY(dra.upload(rect_a, (size_t)n_faces * 4));
-  GLS_TRY(drb.upload(rect_b, (size_t)n_faces * 4));
-  GLS_TRY(dfi.alloc((size_t)std::max<int64_t>(n_faces, 1)));
-  HIP_TRY(gls::launch_kelly_faces(c->dim, m, nodes, c->geo.p, sol, n_faces, dfa.p, dfb.p, dfd.p, dra.p, drb.p,
-                                  pres ? 1 : c->dim, pres ? (int64_t)c->dim * c->n_vnodes : 0, pres ? 1 : c->dim, T,
-                                  dfi.p, c->stream));
-  std::vector<double> fi((size_t)n_faces), geo((size_t)c->n_cells * 4), acc((size_t)c->n_cells, 0.0);
-  HIP_TRY(hipMemcpyAsync(fi.data(), dfi.p, sizeof(double) * fi.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(geo.data(), c->geo.p, sizeof(double) * geo.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int64_t e = 0; e < n_faces; ++e) {  // each piece counts for both of its cells
-    acc[(size_t)fa[e]] += fi[(size_t)e];
-    acc[(size_t)fb[e]] += fi[(size_t)e];
-  }
-  for (int64_t k = 0; k < c->n_cells; ++k) {
-    double d2 = 0.0;
-    for (int d = 0; d < c->dim; ++d) d2 += geo[(size_t)k * 4 + d] * geo[(size_t)k * 4 + d];
-    acc[(size_t)k] = std::sqrt(std::sqrt(d2) / 24.0 * acc[(size_t)k]);
-  }
-  HIP_TRY(hipMemcpyAsync(eta, acc.data(), sizeof(double) * acc.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GLS_OK;
-}
-
-// Kelly indicator on mapped (MappingQ) meshes, conforming or with hanging faces: the face pieces
-// and their per-point geometry from gls_fe_space_kelly_faces (host), the jump integrals on the
-// device, eta_K = sqrt(diam(K)/24 * sum of K's pieces) in a fixed order (eta: DEVICE pointer)
-int gls_kelly_estimate_mapped(gls_ctx *c, const double *sol, int variable, int64_t n_pieces, int nqf, const int32_t *ca,
-                              const int32_t *cb, const double *xi, const double *g, const double *jxw,
-                              const double *cell_diam, double *eta) {
-  GLS_TRY(check_ctx(c));
-  if (!sol || !eta || !cell_diam || (variable != 0 && variable != 1) || n_pieces < 0 ||
-      (n_pieces > 0 && (!ca || !cb || !xi || !g || !jxw)))
-    return set_err(GLS_EINVAL, "gls_kelly_estimate_mapped: bad arguments");
-  const int nq = c->nq1d + 1;  // QGauss<dim-1>(n_q + 1)
-  if (nqf != (c->dim == 3 ? nq * nq : nq))
-    return set_err(GLS_EINVAL, "gls_kelly_estimate_mapped: %d face points per piece, the face rule has %d", nqf,
-                   c->dim == 3 ? nq * nq : nq);
-  for (int64_t e = 0; e < n_pieces; ++e)
-    if (ca[e] < 0 || ca[e] >= c->n_cells || cb[e] < 0 || cb[e] >= c->n_cells)
-      return set_err(GLS_EINVAL, "gls_kelly_estimate_mapped: piece %lld out of range", (long long)e);
-  const bool pres = variable == 1;
-  const int m = pres ? c->kp : c->k;
-  const int32_t *nodes = pres && c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;
-  const gls::KellyTables T = kelly_tables(m, nq);
-  const size_t npts = (size_t)n_pieces * (size_t)nqf;
-  DevBuf<int32_t> dca, dcb;
-  DevBuf<double> dxi, dg, dj, dfi;
-  GLS_TRY(dca.upload(ca, (size_t)n_pieces));
-  GLS_TRY(dcb.upload(cb, (size_t)n_pieces));
-  GLS_TRY(dxi.upload(xi, npts * 2 * c->dim));
-  GLS_TRY(dg.upload(g, npts * 2 * c->dim));
-  GLS_TRY(dj.upload(jxw, npts));
-  GLS_TRY(dfi.alloc((size_t)std::max<int64_t>(n_pieces, 1)));
-  HIP_TRY(gls::launch_kelly_mapped(c->dim, m, nodes, sol, n_pieces, nqf, dca.p, dcb.p, dxi.p, dg.p, dj.p,
-                                   pres ? 1 : c->dim, pres ? (int64_t)c->dim * c->n_vnodes : 0, pres ? 1 : c->dim, T,
-                                   dfi.p, c->stream));
-  std::vector<double> fi((size_t)n_pieces), acc((size_t)c->n_cells, 0.0);
-  HIP_TRY(hipMemcpyAsync(fi.data(), dfi.p, sizeof(double) * fi.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int64_t e = 0; e < n_pieces; ++e) {  // each piece counts for both of its cells
-    acc[(size_t)ca[e]] += fi[(size_t)e];
-    acc[(size_t)cb[e]] += fi[(size_t)e];
-  }
-  for (int64_t k = 0; k < c->n_cells; ++k) acc[(size_t)k] = std::sqrt(cell_diam[k] / 24.0 * acc[(size_t)k]);
-  HIP_TRY(hipMemcpyAsync(eta, acc.data(), sizeof(double) * acc.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GLS_OK;
-}
-
-// --------------------------------------------------------------------------------------------
-// Forces and torques on the boundaries (postprocessing_force.cc, postprocessing_torque.cc): the face
-// data of one mesh uploaded once (plan), every evaluation one pass over all boundaries on the device
-// --------------------------------------------------------------------------------------------
-struct gls_boundary_plan {
-  gls_ctx *ctx = nullptr;
-  int64_t n_faces = 0, n_pts = 0;
-  int nqf = 0, n_slots = 0;
-  DevBuf<int32_t> cell, slot;
-  DevBuf<double> xi, jinv, normal, jxw, xq, cor, partial, out;
-};
-
-namespace {
-int boundary_degrees(gls_ctx *c, const char *who) {
-  if (!gls::boundary_loads_supported(c->dim, c->k, c->kp))
-    return set_err(GLS_EINVAL,
-                   "%s: FE_Q(%d)-FE_Q(%d) in %dD has no load kernel (velocity / pressure orders (1,1), (2,1), (2,2); "
-                   "2D Q3 is not supported)",
-                   who, c->k, c->kp, c->dim);
-  return GLS_OK;
-}
-}  // namespace
-
-int gls_boundary_plan_create(gls_ctx *c, int64_t n_faces, int nqf, const int32_t *cell, const int32_t *slot,
-                             const double *xi, const double *jinv, const double *normal, const double *jxw,
-                             const double *xq, int n_slots, gls_boundary_plan **out) {
-  GLS_TRY(check_ctx(c));
-  if (!out || n_faces < 0 || nqf < 1 || n_slots < 1 || n_slots > 4096 ||
-      (n_faces > 0 && (!cell || !slot || !xi || !jinv || !normal || !jxw || !xq)))
-    return set_err(GLS_EINVAL, "gls_boundary_plan_create: bad arguments");
-  GLS_TRY(boundary_degrees(c, "gls_boundary_plan_create"));
-  for (int64_t f = 0; f < n_faces; ++f)
-    if (cell[f] < 0 || cell[f] >= c->n_cells || slot[f] < -1 || slot[f] >= n_slots)
-      return set_err(GLS_EINVAL, "gls_boundary_plan_create: face %lld: cell %d / slot %d out of range", (long long)f,
-                     cell[f], slot[f]);
-  std::unique_ptr<gls_boundary_plan> p(new gls_boundary_plan);
-  p->ctx = c;
-  p->n_faces = n_faces;
-  p->nqf = nqf;
-  p->n_slots = n_slots;
-  p->n_pts = n_faces * nqf;
-  const size_t np = (size_t)p->n_pts, dim = (size_t)c->dim;
-  GLS_TRY(p->cell.upload(cell, (size_t)n_faces));
-  GLS_TRY(p->slot.upload(slot, (size_t)n_faces));
-  GLS_TRY(p->xi.upload(xi, np * dim));
-  GLS_TRY(p->jinv.upload(jinv, np * dim * dim));
-  GLS_TRY(p->normal.upload(normal, np * dim));
-  GLS_TRY(p->jxw.upload(jxw, np));
-  GLS_TRY(p->xq.upload(xq, np * dim));
-  GLS_TRY(p->cor.alloc((size_t)n_slots * 3));
-  GLS_TRY(p->partial.alloc((size_t)std::max<int64_t>(gls::boundary_loads_blocks(p->n_pts), 1) * n_slots * 6));
-  GLS_TRY(p->out.alloc((size_t)n_slots * 6));
-  *out = p.release();
-  return GLS_OK;
-}
-
-int gls_boundary_plan_destroy(gls_boundary_plan *plan) {
-  delete plan;
-  return GLS_OK;
-}
-
-int gls_boundary_loads(gls_ctx *c, gls_boundary_plan *p, const double *sol, double viscosity, const double *cor,
-                       double *force, double *torque) {
-  GLS_TRY(check_ctx(c));
-  if (!p || p->ctx != c) return set_err(GLS_EINVAL, "gls_boundary_loads: the plan belongs to another context");
-  if (!sol || !cor || !force || !torque) return set_err(GLS_EINVAL, "gls_boundary_loads: bad arguments");
-  GLS_TRY(boundary_degrees(c, "gls_boundary_loads"));
-  const int ns = p->n_slots;
-  std::fill(force, force + 3 * ns, 0.0);
-  std::fill(torque, torque + 3 * ns, 0.0);
-  if (p->n_pts == 0) return GLS_OK;
-  HIP_TRY(hipMemcpyAsync(p->cor.p, cor, sizeof(double) * 3 * (size_t)ns, hipMemcpyHostToDevice, c->stream));
-  const int32_t *pn = c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;  // equal order: shared nodes
-  HIP_TRY(gls::launch_boundary_loads(c->dim, c->k, c->kp, c->cell_vnodes.p, pn, sol, (int64_t)c->dim * c->n_vnodes,
-                                     p->n_pts, p->nqf, p->cell.p, p->slot.p, p->xi.p, p->jinv.p, p->normal.p, p->jxw.p,
-                                     p->xq.p, viscosity, p->cor.p, ns, p->partial.p, p->out.p, c->stream));
-  std::vector<double> o((size_t)ns * 6);
-  HIP_TRY(hipMemcpyAsync(o.data(), p->out.p, sizeof(double) * o.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int s = 0; s < ns; ++s)
-    for (int i = 0; i < 3; ++i) {
-      force[3 * s + i] = o[(size_t)(6 * s + i)];
-      torque[3 * s + i] = o[(size_t)(6 * s + 3 + i)];
-    }
-  return GLS_OK;
-}
-
-// --------------------------------------------------------------------------------------------
-// Flow diagnostics (postprocessing_cfl.cc, postprocessing_kinetic_energy.cc, postprocessing_enstrophy.cc):
-// one pass over the context's cells, per-block partials and one ordered stage on the device
-// --------------------------------------------------------------------------------------------
-int gls_flow_diagnostics(gls_ctx *c, const double *sol, double dt, double out[4]) {
-  GLS_TRY(check_ctx(c));
-  if (!sol || !out) return set_err(GLS_EINVAL, "gls_flow_diagnostics: bad arguments");
-  if (!gls::flow_diagnostics_supported(c->dim, c->k, c->kp) || c->nq1d != c->k + 1)
-    return set_err(GLS_EINVAL,
-                   "gls_flow_diagnostics: FE_Q(%d)-FE_Q(%d) in %dD with QGauss(%d) has no diagnostics kernel (velocity / "
-                   "pressure orders (1,1), (2,1), (2,2) with QGauss(k+1); 2D Q3 is not supported)",
-                   c->k, c->kp, c->dim, c->nq1d);
-  for (int i = 0; i < 4; ++i) out[i] = 0.0;
-  if (c->n_cells == 0) return GLS_OK;
-  if (!c->fd_out.p) {  // once per context: cell measures, 1D tables, partials
-    const int dim = c->dim, k1 = c->k + 1;
-    std::vector<double> meas((size_t)c->n_cells, 1.0);
-    if (c->map_degree > 0) {
-      const size_t nsup = (size_t)gls::ipow(c->map_degree + 1, dim);
-      for (int cix = 0; cix < c->n_cells; ++cix)
-        meas[(size_t)cix] = corner_measure(dim, c->map_degree, c->host_support.data() + (size_t)cix * nsup * dim);
-    } else {
-      for (int cix = 0; cix < c->n_cells; ++cix)
-        for (int e = 0; e < dim; ++e) meas[(size_t)cix] *= c->host_h[(size_t)cix * dim + e];
-    }
-    std::vector<double> tab((size_t)(2 * k1 * k1 + k1));
-    for (int q = 0; q < k1; ++q) {
-      for (int a = 0; a < k1; ++a) {
-        tab[(size_t)(q * k1 + a)] = c->tables.V[q][a];
-        tab[(size_t)(k1 * k1 + q * k1 + a)] = c->tables.D[q][a];
-      }
-      tab[(size_t)(2 * k1 * k1 + q)] = c->tables.w[q];
-    }
-    GLS_TRY(c->fd_meas.upload(meas.data(), meas.size()));
-    GLS_TRY(c->fd_tab.upload(tab.data(), tab.size()));
-    GLS_TRY(c->fd_partial.alloc((size_t)gls::flow_diagnostics_blocks(c->n_cells) * 4));
-    GLS_TRY(c->fd_out.alloc(4));
-  }
-  HIP_TRY(gls::launch_flow_diagnostics(c->dim, c->k, c->cell_vnodes.p, c->geo.p, c->gq.p, c->fd_meas.p, c->fd_tab.p, sol,
-                                       c->n_cells, dt, c->fd_partial.p, c->fd_out.p, c->stream));
-  HIP_TRY(hipMemcpyAsync(out, c->fd_out.p, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GLS_OK;
-}
-
-// --------------------------------------------------------------------------------------------
-// VTU point data on the device (navier_stokes_base.cc:1035-1064, post_processors.h:27-171): the geometry of
-// one mesh and the 1D tables at the patch points uploaded once (plan), every output one launch over all
-// cells, one download per array and the file writer of gls_vtu_write
-// --------------------------------------------------------------------------------------------
-}  // extern "C"
-// gls_io.cpp: the 1D tables and the file writer shared with gls_vtu_write
-void gls_io_patch_tables(int degree, int ns, double *V, double *D);
-int gls_io_vtu_write_piece(const char *filename, int dim, int k, int64_t nc, int ns, int subdomain, int binary, int srf,
-                           const double *pts, const double *vel, const double *pre, const double *vort,
-                           const double *qcr, const double *eul, double *encode_seconds);
-extern "C" {
-
-struct gls_output_plan {
-  gls_ctx *ctx = nullptr;
-  int ns = 1, srf = 0;
-  double omega[3] = {0, 0, 0};
-  int64_t n_pts = 0;
-  DevBuf<double> x0h, support, tab;
-  DevBuf<double> pts, vel, pre, vort, qcr, eul;  // the device field buffers, allocated once
-  std::vector<double> h_pts, h_vel, h_pre, h_vort, h_qcr, h_eul;  // gls_vtu_write_device: the downloaded arrays
-};
-
-int gls_output_plan_create(gls_ctx *c, const gls_mesh_desc *m, int subdivision, gls_output_plan **out) {
-  GLS_TRY(check_ctx(c));
-  if (!m || !out) return set_err(GLS_EINVAL, "gls_output_plan_create: null argument");
-  if (m->dim != c->dim || m->k != c->k || m->kp != c->kp || m->n_cells != c->n_cells || m->map_degree != c->map_degree)
-    return set_err(GLS_EINVAL,
-                   "gls_output_plan_create: the mesh (%dD FE_Q(%d)-FE_Q(%d), %d cells, mapping degree %d) is not the "
-                   "context's (%dD FE_Q(%d)-FE_Q(%d), %d cells, mapping degree %d)",
-                   m->dim, m->k, m->kp, m->n_cells, m->map_degree, c->dim, c->k, c->kp, c->n_cells, c->map_degree);
-  if (!gls::output_fields_supported(c->dim, c->k, c->kp, c->map_degree, subdivision))
-    return set_err(GLS_EINVAL,
-                   "gls_output_plan_create: FE_Q(%d)-FE_Q(%d) in %dD with subdivision %d has no output kernel (velocity / "
-                   "pressure orders (1,1), (2,1), (2,2), 2D Q3 is not supported; (subdivision+1)^dim <= 256: subdivision "
-                   "1..15 in 2D, 1..5 in 3D)",
-                   c->k, c->kp, c->dim, subdivision);
-  const int dim = c->dim, md = c->map_degree, np1 = subdivision + 1;
-  if (md ? !m->cell_support : !m->cell_h)
-    return set_err(GLS_EINVAL, "gls_output_plan_create: the mesh has no %s", md ? "cell_support" : "cell_h");
-  std::unique_ptr<gls_output_plan> p(new gls_output_plan);
-  p->ctx = c;
-  p->ns = subdivision;
-  p->srf = m->srf ? 1 : 0;
-  for (int i = 0; i < 3; ++i) p->omega[i] = m->omega[i];
-  const size_t nc = (size_t)c->n_cells;
-  p->n_pts = (int64_t)nc * gls::ipow(np1, dim);
-  if (md) {
-    GLS_TRY(p->support.upload(m->cell_support, nc * (size_t)gls::ipow(md + 1, dim) * dim));
-  } else {
-    std::vector<double> x0h(nc * 2 * dim);
-    for (size_t cix = 0; cix < nc; ++cix)
-      for (int d = 0; d < dim; ++d) {
-        x0h[cix * 2 * dim + d] = m->cell_x0 ? m->cell_x0[cix * dim + d] : 0.0;
-        x0h[cix * 2 * dim + dim + d] = m->cell_h[cix * dim + d];
-      }
-    GLS_TRY(p->x0h.upload(x0h.data(), x0h.size()));
-  }
-  // Vv | Dv | Vp | Vm | Dm at t / subdivision
-  const int k1 = c->k + 1, kp1 = c->kp + 1, nm = md ? md + 1 : 0;
-  std::vector<double> tab((size_t)np1 * (2 * k1 + kp1 + 2 * nm));
-  gls_io_patch_tables(c->k, subdivision, tab.data(), tab.data() + np1 * k1);
-  gls_io_patch_tables(c->kp, subdivision, tab.data() + 2 * np1 * k1, nullptr);  // the pressure enters by value only
-  if (md) gls_io_patch_tables(md, subdivision, tab.data() + np1 * (2 * k1 + kp1), tab.data() + np1 * (2 * k1 + kp1 + nm));
-  GLS_TRY(p->tab.upload(tab.data(), tab.size()));
-  const size_t np = (size_t)p->n_pts;
-  GLS_TRY(p->pts.alloc(np * 3));
-  GLS_TRY(p->vel.alloc(np * 3));
-  GLS_TRY(p->pre.alloc(np));
-  GLS_TRY(p->vort.alloc(np * (dim == 3 ? 3 : 1)));
-  GLS_TRY(p->qcr.alloc(np));
-  if (p->srf) GLS_TRY(p->eul.alloc(np * 3));
-  *out = p.release();
-  return GLS_OK;
-}
-
-int gls_output_plan_destroy(gls_output_plan *plan) {
-  delete plan;
-  return GLS_OK;
-}
-
-namespace {
-// the launch and one download per array, all on the context's stream; the caller synchronizes
-int output_fields_queue(gls_ctx *c, gls_output_plan *p, const double *sol, double *pts, double *vel, double *pre,
-                        double *vort, double *qcr, double *eul) {
-  const size_t np = (size_t)p->n_pts;
-  if (np == 0) return GLS_OK;
-  if (!c->cell_pnodes.p && c->kp != c->k) return set_err(GLS_EINVAL, "output fields: the context has no cell_pnodes");
-  const int32_t *pn = c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;  // equal order: shared nodes
-  HIP_TRY(gls::launch_output_fields(c->dim, c->k, c->kp, c->map_degree, p->ns, c->cell_vnodes.p, pn, sol,
-                                    (int64_t)c->dim * c->n_vnodes, p->x0h.p, p->support.p, p->tab.p, c->n_cells, p->srf,
-                                    p->omega, p->pts.p, p->vel.p, p->pre.p, p->vort.p, p->qcr.p, p->eul.p, c->stream));
-  const struct { double *h; const double *d; size_t n; } a[6] = {
-      {pts, p->pts.p, np * 3}, {vel, p->vel.p, np * 3}, {pre, p->pre.p, np}, {vort, p->vort.p, np * (c->dim == 3 ? 3 : 1)},
-      {qcr, p->qcr.p, np},     {p->srf ? eul : nullptr, p->eul.p, np * 3}};
-  for (const auto &x : a)
-    if (x.h) HIP_TRY(hipMemcpyAsync(x.h, x.d, sizeof(double) * x.n, hipMemcpyDeviceToHost, c->stream));
-  return GLS_OK;
-}
-int output_plan_check(gls_ctx *c, gls_output_plan *p, const double *sol, const char *who) {
-  GLS_TRY(check_ctx(c));
-  if (!p || p->ctx != c) return set_err(GLS_EINVAL, "%s: the plan belongs to another context", who);
-  if (!sol) return set_err(GLS_EINVAL, "%s: null solution", who);
-  if (p->n_pts != (int64_t)c->n_cells * gls::ipow(p->ns + 1, c->dim))
-    return set_err(GLS_EINVAL, "%s: the context has changed since the plan was made", who);
-  return GLS_OK;
-}
-}  // namespace
-
-int gls_output_fields(gls_ctx *c, gls_output_plan *p, const double *sol, double *points, double *velocity,
-                      double *pressure, double *vorticity, double *q_criterion, double *velocity_eulerian) {
-  GLS_TRY(output_plan_check(c, p, sol, "gls_output_fields"));
-  if (!points || !velocity || !pressure || !vorticity || !q_criterion || (p->srf && !velocity_eulerian))
-    return set_err(GLS_EINVAL, "gls_output_fields: null output array");
-  GLS_TRY(output_fields_queue(c, p, sol, points, velocity, pressure, vorticity, q_criterion, velocity_eulerian));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return GLS_OK;
-}
-
-int gls_vtu_write_device(gls_ctx *c, gls_output_plan *p, const double *sol, const char *filename, int subdomain,
-                         int binary) {
-  GLS_TRY(output_plan_check(c, p, sol, "gls_vtu_write_device"));
-  if (!filename) return set_err(GLS_EINVAL, "gls_vtu_write_device: null file name");
-  // GLS_OUTPUT_SPLIT=1: host clocks to the synchronization, around the encoding and over the writer, on stderr
-  static const bool split = std::getenv("GLS_OUTPUT_SPLIT") != nullptr;
-  double enc = 0.0;
-  const auto t0 = std::chrono::steady_clock::now();
-  const size_t np = (size_t)p->n_pts;
-  if (p->h_pts.size() != np * 3) {  // once per plan
-    p->h_pts.resize(np * 3);
-    p->h_vel.resize(np * 3);
-    p->h_pre.resize(np);
-    p->h_vort.resize(np * (c->dim == 3 ? 3 : 1));
-    p->h_qcr.resize(np);
-    if (p->srf) p->h_eul.resize(np * 3);
-  }
-  GLS_TRY(output_fields_queue(c, p, sol, p->h_pts.data(), p->h_vel.data(), p->h_pre.data(), p->h_vort.data(),
-                              p->h_qcr.data(), p->h_eul.data()));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  const auto t1 = std::chrono::steady_clock::now();
-  const int rc = gls_io_vtu_write_piece(filename, c->dim, c->k, c->n_cells, p->ns, subdomain, binary, p->srf,
-                                        p->h_pts.data(), p->h_vel.data(), p->h_pre.data(), p->h_vort.data(),
-                                        p->h_qcr.data(), p->srf ? p->h_eul.data() : nullptr, split ? &enc : nullptr);
-  if (split) {
-    const double dl = std::chrono::duration<double>(t1 - t0).count();
-    const double wr = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-    std::fprintf(stderr, "gls_vtu_write_device: launch + downloads %.6f s, encode %.6f s, file write %.6f s\n", dl, enc,
-                 wr - enc);
-  }
-  return rc;
-}
 
 int gls_set_lattice(gls_ctx *c, int n1d, const int64_t *l2g) {
   GLS_TRY(check_ctx(c));
@@ -5129,1031 +3962,3 @@ int gls_timing_get(gls_ctx *c, int which, double *ms, int64_t *cnt) {
 }
 
 }  // extern "C"
-
-
-// ---------------------------------------------------------------------------------------------
-// gls_ilu_attach: the reference's ILU-preconditioned GMRES (linear solver method gmres with 'ilu
-// preconditioner fill / absolute tolerance / relative tolerance', setup_ILU gls_navier_stokes.cc:
-// 1161-1176: Ifpack ILU(k) with athresh / rthresh, no overlap) on the assembled Jacobian. The matrix
-// is never formed by a CPU: it is probed from the device operator with distance-2-colored unit
-// vectors (no two DoFs of a probe share a row). Its graph is the reference's system-matrix sparsity
-// (make_sparsity_pattern with nonzero_constraints, keep_constrained_dofs = false,
-// gls_navier_stokes.cc:208-211): a constrained row / column holds its diagonal only, lines
-// (hanging nodes, slip on curved walls) couple their masters. The DoFs are renumbered like
-// DoFRenumbering::Cuthill_McKee (gls_navier_stokes.cc:70), the level-of-fill pattern of ILU(fill)
-// is inserted with explicit zeros, and rocSPARSE csrilu0 on that pattern computes ILU(fill).
-// ---------------------------------------------------------------------------------------------
-extern "C" int gls_ilu_attach(gls_ctx *c, int fill, double athresh, double rthresh) {
-  GLS_TRY(check_ctx(c));
-  auto &I = c->ilu;
-  I.probe_only = false;  // a caller's attach: a preconditioner (mg_probe_setup marks its own afterwards)
-  if (c->dist.on && !c->dist.dofs) return set_err(GLS_EINVAL, "gls_ilu_attach: brick-partitioned contexts use the multigrid");
-  if (c->mg.on) return set_err(GLS_EINVAL, "gls_ilu_attach: a multigrid preconditioner is attached");
-  if (fill < 0 || fill > GLS_ILU_MAX_FILL)
-    return set_err(GLS_EINVAL, "gls_ilu_attach: ilu preconditioner fill %d not supported (0..%d)", fill, GLS_ILU_MAX_FILL);
-  const int dim = c->dim, nvc = gls::ipow(c->k + 1, dim);
-  const bool sep = c->cell_pnodes.p != nullptr;
-  const int npc = sep ? gls::ipow(c->kp + 1, dim) : 0;
-  const int64_t nv = c->n_vnodes, np = c->n_pnodes, nc = c->n_cells, n = c->n_dofs;
-  if (n >= INT32_MAX) return set_err(GLS_EINVAL, "gls_ilu_attach: too many DoFs for 32-bit CSR");
-  std::vector<int32_t> cv((size_t)nc * nvc), cp((size_t)nc * npc);
-  HIP_TRY(hipMemcpy(cv.data(), c->cell_vnodes.p, cv.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (sep) HIP_TRY(hipMemcpy(cp.data(), c->cell_pnodes.p, cp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  // unified nodes: velocity nodes [0, nv), separate pressure nodes [nv, nv + np)
-  const int64_t nu = nv + (sep ? np : 0);
-  const int ncn = nvc + npc;
-  auto cell_node = [&](int64_t cell, int a) -> int64_t {
-    return a < nvc ? cv[(size_t)(cell * nvc + a)] : nv + cp[(size_t)(cell * npc + a - nvc)];
-  };
-  // DoFs of a unified node and their probe slot (component; dim = pressure)
-  auto node_dofs = [&](int64_t x, int64_t *d, int *slot) -> int {
-    if (x >= nv) { d[0] = dim * nv + (x - nv); slot[0] = dim; return 1; }
-    int m = 0;
-    for (int cc = 0; cc < dim; ++cc) { d[m] = x * dim + cc; slot[m++] = cc; }
-    if (!sep) { d[m] = dim * nv + x; slot[m++] = dim; }
-    return m;
-  };
-  const int64_t nvd = (int64_t)dim * nv;
-  auto unode = [&](int64_t d) { return d < nvd ? d / dim : (sep ? nv + (d - nvd) : d - nvd); };
-  // constrained DoFs (zero_constraints: Dirichlet + lines) and the operator lines (Dirichlet masters
-  // drop out, as in the closed AffineConstraints)
-  std::vector<char> cons((size_t)n, 0), isline((size_t)n, 0);
-  {
-    std::vector<int64_t> cd(c->con_dofs.n);
-    if (!cd.empty()) HIP_TRY(hipMemcpy(cd.data(), c->con_dofs.p, cd.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-    for (int64_t d : cd) cons[(size_t)d] = 1;
-  }
-  std::vector<int64_t> lidx((size_t)n, -1);
-  if (c->hang.on)
-    for (size_t i = 0; i + 1 < c->hang.h_off.size(); ++i) {
-      lidx[(size_t)c->hang.h_dof[i]] = (int64_t)i;
-      isline[(size_t)c->hang.h_dof[i]] = 1;
-    }
-  // across ranks (Ifpack additive Schwarz, overlap 0, as the reference runs with MPI): each rank
-  // factors its owned rows and columns; ghost DoFs are identity rows and drop out of the pattern
-  auto ghost = [&](int64_t d) {
-    if (!c->dist.on) return false;
-    return d < nvd ? d / dim >= c->dist.n_owned : d - nvd >= c->dist.n_owned_p;
-  };
-  const std::vector<char> fcons = cons;  // constrained DoFs before the ghosts join them (complete rows)
-  for (int64_t d = 0; d < n; ++d)
-    if (ghost(d)) cons[(size_t)d] = 1;
-  auto dirichlet = [&](int64_t d) { return (cons[(size_t)d] && !isline[(size_t)d]) || ghost(d); };
-  // effective DoFs of each cell: its unconstrained DoFs and the (non-Dirichlet) masters of its lines
-  std::vector<int64_t> effoff((size_t)nc + 1, 0), eff;
-  {
-    std::vector<int64_t> buf;
-    for (int64_t e = 0; e < nc; ++e) {
-      buf.clear();
-      for (int a = 0; a < ncn; ++a) {
-        int64_t d[4];
-        int sl[4];
-        const int m = node_dofs(cell_node(e, a), d, sl);
-        for (int j = 0; j < m; ++j) {
-          const int64_t li = lidx[(size_t)d[j]];
-          if (li >= 0 && !ghost(d[j])) {
-            for (int64_t t = c->hang.h_off[(size_t)li]; t < c->hang.h_off[(size_t)li + 1]; ++t)
-              if (!dirichlet(c->hang.h_master[(size_t)t])) buf.push_back(c->hang.h_master[(size_t)t]);
-          } else if (!cons[(size_t)d[j]]) {
-            buf.push_back(d[j]);
-          }
-        }
-      }
-      std::sort(buf.begin(), buf.end());
-      buf.erase(std::unique(buf.begin(), buf.end()), buf.end());
-      eff.insert(eff.end(), buf.begin(), buf.end());
-      effoff[(size_t)e + 1] = (int64_t)eff.size();
-    }
-  }
-  // DoF -> cells whose effective list holds it
-  std::vector<int64_t> dcoff((size_t)n + 1, 0), dcell;
-  for (int64_t d : eff) ++dcoff[(size_t)d + 1];
-  for (int64_t i = 0; i < n; ++i) dcoff[(size_t)i + 1] += dcoff[(size_t)i];
-  dcell.resize((size_t)dcoff[(size_t)n]);
-  {
-    std::vector<int64_t> f(dcoff.begin(), dcoff.end() - 1);
-    for (int64_t e = 0; e < nc; ++e)
-      for (int64_t t = effoff[(size_t)e]; t < effoff[(size_t)e + 1]; ++t) dcell[(size_t)f[(size_t)eff[(size_t)t]]++] = e;
-  }
-  // rows of the system matrix (old numbering, sorted): an unconstrained DoF couples the effective DoFs
-  // of its cells; a constrained DoF only itself
-  std::vector<int64_t> aoff((size_t)n + 1, 0), acol;
-  {
-    std::vector<int64_t> stamp((size_t)n, -1), buf;
-    for (int64_t i = 0; i < n; ++i) {
-      buf.clear();
-      buf.push_back(i);
-      stamp[(size_t)i] = i;
-      if (!cons[(size_t)i])
-        for (int64_t t = dcoff[(size_t)i]; t < dcoff[(size_t)i + 1]; ++t) {
-          const int64_t e = dcell[(size_t)t];
-          for (int64_t u = effoff[(size_t)e]; u < effoff[(size_t)e + 1]; ++u) {
-            const int64_t j = eff[(size_t)u];
-            if (stamp[(size_t)j] != i) { stamp[(size_t)j] = i; buf.push_back(j); }
-          }
-        }
-      std::sort(buf.begin(), buf.end());
-      acol.insert(acol.end(), buf.begin(), buf.end());
-      aoff[(size_t)i + 1] = (int64_t)acol.size();
-    }
-  }
-  // node graph of that pattern (x ~ y when a row of x holds a DoF of y) for the distance-2 coloring
-  std::vector<int64_t> n1off((size_t)nu + 1, 0), n1;
-  {
-    std::vector<int64_t> stamp((size_t)nu, -1), buf;
-    for (int64_t x = 0; x < nu; ++x) {
-      buf.clear();
-      buf.push_back(x);
-      stamp[(size_t)x] = x;
-      int64_t d[4];
-      int sl[4];
-      const int m = node_dofs(x, d, sl);
-      for (int j = 0; j < m; ++j)
-        for (int64_t t = aoff[(size_t)d[j]]; t < aoff[(size_t)d[j] + 1]; ++t) {
-          const int64_t y = unode(acol[(size_t)t]);
-          if (stamp[(size_t)y] != x) { stamp[(size_t)y] = x; buf.push_back(y); }
-        }
-      std::sort(buf.begin(), buf.end());
-      n1.insert(n1.end(), buf.begin(), buf.end());
-      n1off[(size_t)x + 1] = (int64_t)n1.size();
-    }
-  }
-  // greedy distance-2 coloring of the unified nodes
-  std::vector<int> color((size_t)nu, -1), mark;
-  int ncol = 0;
-  for (int64_t x = 0; x < nu; ++x) {
-    for (int64_t t = n1off[(size_t)x]; t < n1off[(size_t)x + 1]; ++t) {
-      const int64_t z = n1[(size_t)t];
-      for (int64_t u = n1off[(size_t)z]; u < n1off[(size_t)z + 1]; ++u) {
-        const int cy = color[(size_t)n1[(size_t)u]];
-        if (cy >= 0) {
-          if ((int)mark.size() <= cy) mark.resize((size_t)cy + 1, -1);
-          mark[(size_t)cy] = (int)x;
-        }
-      }
-    }
-    int col = 0;
-    while (col < (int)mark.size() && mark[(size_t)col] == (int)x) ++col;
-    color[(size_t)x] = col;
-    ncol = std::max(ncol, col + 1);
-  }
-  // Across ranks, complete owned rows (the rows of Ifpack's distributed matrix, restricted to the owned
-  // columns as its additive Schwarz with overlap 0 does): the owned x owned block also receives the
-  // neighbours' cells. Every rank probes its cells' operator on ALL its DoFs (owned and ghost) with a
-  // distance-2 coloring of that full local pattern; the ghost rows of each probe go to their owners
-  // through the export exchange, tagged once (here) with the column as its position in the owner's
-  // send list. Probe rounds run to the largest probe count of any rank (collective).
-  std::vector<char> aown;  // per system-matrix entry: probed on this rank (else a neighbour's entry only)
-  struct RemoteEntry {
-    int32_t round, slot;
-    int64_t i, j;
-  };
-  std::vector<RemoteEntry> remote;
-  int n_rounds = 0;
-  const bool cmpl = c->dist.on && c->dist.dofs;
-  if (cmpl) {
-    auto fdir = [&](int64_t d) { return fcons[(size_t)d] && !isline[(size_t)d]; };
-    std::vector<int64_t> feoff((size_t)nc + 1, 0), feff, buf;
-    for (int64_t e = 0; e < nc; ++e) {
-      buf.clear();
-      for (int a = 0; a < ncn; ++a) {
-        int64_t d[4];
-        int sl[4];
-        const int m = node_dofs(cell_node(e, a), d, sl);
-        for (int j = 0; j < m; ++j) {
-          const int64_t li = lidx[(size_t)d[j]];
-          if (li >= 0) {
-            for (int64_t t = c->hang.h_off[(size_t)li]; t < c->hang.h_off[(size_t)li + 1]; ++t)
-              if (!fdir(c->hang.h_master[(size_t)t])) buf.push_back(c->hang.h_master[(size_t)t]);
-          } else if (!fcons[(size_t)d[j]]) {
-            buf.push_back(d[j]);
-          }
-        }
-      }
-      std::sort(buf.begin(), buf.end());
-      buf.erase(std::unique(buf.begin(), buf.end()), buf.end());
-      feff.insert(feff.end(), buf.begin(), buf.end());
-      feoff[(size_t)e + 1] = (int64_t)feff.size();
-    }
-    std::vector<int64_t> fdoff((size_t)n + 1, 0), fdcell;
-    for (int64_t d : feff) ++fdoff[(size_t)d + 1];
-    for (int64_t i = 0; i < n; ++i) fdoff[(size_t)i + 1] += fdoff[(size_t)i];
-    fdcell.resize((size_t)fdoff[(size_t)n]);
-    {
-      std::vector<int64_t> f(fdoff.begin(), fdoff.end() - 1);
-      for (int64_t e = 0; e < nc; ++e)
-        for (int64_t t = feoff[(size_t)e]; t < feoff[(size_t)e + 1]; ++t) fdcell[(size_t)f[(size_t)feff[(size_t)t]]++] = e;
-    }
-    std::vector<int64_t> faoff((size_t)n + 1, 0), facol;
-    {
-      std::vector<int64_t> stamp((size_t)n, -1);
-      for (int64_t i = 0; i < n; ++i) {
-        buf.clear();
-        buf.push_back(i);
-        stamp[(size_t)i] = i;
-        if (!fcons[(size_t)i])
-          for (int64_t t = fdoff[(size_t)i]; t < fdoff[(size_t)i + 1]; ++t) {
-            const int64_t e = fdcell[(size_t)t];
-            for (int64_t u = feoff[(size_t)e]; u < feoff[(size_t)e + 1]; ++u) {
-              const int64_t j = feff[(size_t)u];
-              if (stamp[(size_t)j] != i) { stamp[(size_t)j] = i; buf.push_back(j); }
-            }
-          }
-        std::sort(buf.begin(), buf.end());
-        facol.insert(facol.end(), buf.begin(), buf.end());
-        faoff[(size_t)i + 1] = (int64_t)facol.size();
-      }
-    }
-    // distance-2 coloring of the full pattern's node graph (replaces the owned-block coloring)
-    std::vector<int64_t> g1off((size_t)nu + 1, 0), g1;
-    {
-      std::vector<int64_t> stamp((size_t)nu, -1);
-      for (int64_t x = 0; x < nu; ++x) {
-        buf.clear();
-        buf.push_back(x);
-        stamp[(size_t)x] = x;
-        int64_t d[4];
-        int sl[4];
-        const int m = node_dofs(x, d, sl);
-        for (int j = 0; j < m; ++j)
-          for (int64_t t = faoff[(size_t)d[j]]; t < faoff[(size_t)d[j] + 1]; ++t) {
-            const int64_t y = unode(facol[(size_t)t]);
-            if (stamp[(size_t)y] != x) { stamp[(size_t)y] = x; buf.push_back(y); }
-          }
-        std::sort(buf.begin(), buf.end());
-        g1.insert(g1.end(), buf.begin(), buf.end());
-        g1off[(size_t)x + 1] = (int64_t)g1.size();
-      }
-    }
-    std::fill(color.begin(), color.end(), -1);
-    mark.clear();
-    ncol = 0;
-    for (int64_t x = 0; x < nu; ++x) {
-      for (int64_t t = g1off[(size_t)x]; t < g1off[(size_t)x + 1]; ++t) {
-        const int64_t z = g1[(size_t)t];
-        for (int64_t u = g1off[(size_t)z]; u < g1off[(size_t)z + 1]; ++u) {
-          const int cy = color[(size_t)g1[(size_t)u]];
-          if (cy >= 0) {
-            if ((int)mark.size() <= cy) mark.resize((size_t)cy + 1, -1);
-            mark[(size_t)cy] = (int)x;
-          }
-        }
-      }
-      int col = 0;
-      while (col < (int)mark.size() && mark[(size_t)col] == (int)x) ++col;
-      color[(size_t)x] = col;
-      ncol = std::max(ncol, col + 1);
-    }
-    auto pof = [&](int64_t d) { return color[(size_t)unode(d)] * (dim + 1) + (d < nvd ? (int)(d % dim) : dim); };
-    const int nprobe_local = ncol * (dim + 1);
-    // the column tags: per round, each ghost row's probed column as its position in the owner's list
-    auto &D = c->dist;
-    const int nn = (int)D.h_soff.size() - 1;
-    const int64_t ns = D.n_send, nr = D.n_recv;
-    std::vector<int32_t> gnb((size_t)n, -1), gk((size_t)n, -1);
-    for (int t = 0; t < nn; ++t)
-      for (int64_t q = D.h_roff[(size_t)t]; q < D.h_roff[(size_t)t + 1]; ++q) {
-        gnb[(size_t)D.h_recv[(size_t)q]] = t;
-        gk[(size_t)D.h_recv[(size_t)q]] = (int32_t)(q - D.h_roff[(size_t)t]);
-      }
-    std::vector<double> hpos((size_t)std::max<int64_t>(nr, 1)), hin((size_t)std::max<int64_t>(ns, 1));
-    for (int p = 0;; ++p) {
-      double flag = p < nprobe_local ? 1.0 : 0.0;
-      HIP_TRY(hipMemcpy(D.red_buf, &flag, sizeof(double), hipMemcpyHostToDevice));
-      if (D.allreduce(D.user, D.red_buf, 1) != 0) return set_err(GLS_ECOMM, "gls_ilu_attach: allreduce failed");
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      HIP_TRY(hipMemcpy(&flag, D.red_buf, sizeof(double), hipMemcpyDeviceToHost));
-      if (flag == 0.0) break;
-      ++n_rounds;
-      for (int64_t q = 0; q < nr; ++q) {
-        const int64_t i = D.h_recv[(size_t)q];
-        double pos = -1.0;
-        if (p < nprobe_local && !fcons[(size_t)i])
-          for (int64_t t = faoff[(size_t)i]; t < faoff[(size_t)i + 1]; ++t) {
-            const int64_t j = facol[(size_t)t];
-            if (pof(j) != p) continue;
-            if (gnb[(size_t)j] == gnb[(size_t)i]) pos = (double)gk[(size_t)j];
-            break;
-          }
-        hpos[(size_t)q] = pos;
-      }
-      if (nr) HIP_TRY(hipMemcpy(D.recv_buf, hpos.data(), sizeof(double) * (size_t)nr, hipMemcpyHostToDevice));
-      HIP_TRY(hipDeviceSynchronize());
-      if (D.xchg(D.user, 1) != 0) return set_err(GLS_ECOMM, "gls_ilu_attach: exchange failed");
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (ns) HIP_TRY(hipMemcpy(hin.data(), D.send_buf, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost));
-      for (int t = 0; t < nn; ++t)
-        for (int64_t q = D.h_soff[(size_t)t]; q < D.h_soff[(size_t)t + 1]; ++q) {
-          const int64_t pos = (int64_t)hin[(size_t)q];
-          if (pos < 0) continue;
-          if (pos >= D.h_soff[(size_t)t + 1] - D.h_soff[(size_t)t]) return set_err(GLS_ECOMM, "gls_ilu_attach: bad column tag");
-          const int64_t i = D.h_send[(size_t)q], j = D.h_send[(size_t)(D.h_soff[(size_t)t] + pos)];
-          if (cons[(size_t)i] || cons[(size_t)j]) continue;
-          remote.push_back({p, (int32_t)q, i, j});
-        }
-    }
-    // the system matrix's rows gain the neighbours' couplings
-    std::vector<std::vector<int64_t>> extra((size_t)n);
-    for (const auto &r : remote) extra[(size_t)r.i].push_back(r.j);
-    std::vector<int64_t> noff((size_t)n + 1, 0), ncl_;
-    for (int64_t i = 0; i < n; ++i) {
-      const size_t s0 = ncl_.size();
-      for (int64_t t = aoff[(size_t)i]; t < aoff[(size_t)i + 1]; ++t) ncl_.push_back(acol[(size_t)t]);
-      auto &x = extra[(size_t)i];
-      std::sort(x.begin(), x.end());
-      for (int64_t j : x)
-        if (!std::binary_search(acol.begin() + aoff[(size_t)i], acol.begin() + aoff[(size_t)i + 1], j)) ncl_.push_back(j);
-      std::sort(ncl_.begin() + (std::ptrdiff_t)s0, ncl_.end());
-      ncl_.erase(std::unique(ncl_.begin() + (std::ptrdiff_t)s0, ncl_.end()), ncl_.end());
-      noff[(size_t)i + 1] = (int64_t)ncl_.size();
-    }
-    aown.assign(ncl_.size(), 0);
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t t = noff[(size_t)i]; t < noff[(size_t)i + 1]; ++t)
-        aown[(size_t)t] = std::binary_search(acol.begin() + aoff[(size_t)i], acol.begin() + aoff[(size_t)i + 1], ncl_[(size_t)t]);
-    aoff.swap(noff);
-    acol.swap(ncl_);
-  } else {
-    aown.assign(acol.size(), 1);
-  }
-  // Cuthill-McKee (deal.II) on the unconstrained cell-coupling graph of the DoF handler. Its nodes
-  // carry deal.II's per-support-point DoF groups: a velocity node's components followed by the
-  // pressure DoF at the same point (Q(k)-Q(kp) with kp | k: a pressure node sits on the velocity node
-  // of the same lexicographic position in every cell; the map is checked cell by cell)
-  std::vector<int64_t> p_at((size_t)std::max<int64_t>(np, 1), -1);  // pressure node -> velocity node
-  bool p_map = sep && c->k % c->kp == 0;
-  if (p_map) {
-    const int r = c->k / c->kp, k1 = c->k + 1, kp1 = c->kp + 1;
-    for (int64_t e = 0; e < nc && p_map; ++e)
-      for (int a = 0; a < npc; ++a) {
-        const int ax = a % kp1, ay = (a / kp1) % kp1, az = dim == 3 ? a / (kp1 * kp1) : 0;
-        const int va = ax * r + k1 * (ay * r) + (dim == 3 ? k1 * k1 * az * r : 0);
-        const int64_t pn = cp[(size_t)(e * npc + a)], vn = cv[(size_t)(e * nvc + va)];
-        if (p_at[(size_t)pn] < 0) p_at[(size_t)pn] = vn;
-        else if (p_at[(size_t)pn] != vn) { p_map = false; break; }
-      }
-  }
-  // CM nodes: velocity nodes (+ their pressure DoF), then unmapped pressure nodes
-  std::vector<int64_t> cmnode((size_t)nu, -1);  // unified node -> CM node
-  int64_t ncm = 0;
-  for (int64_t x = 0; x < nv; ++x) cmnode[(size_t)x] = ncm++;
-  if (sep)
-    for (int64_t pn = 0; pn < np; ++pn)  // (a ghost pressure node in no local cell -- a line master only -- is its own node)
-      cmnode[(size_t)(nv + pn)] = p_map && p_at[(size_t)pn] >= 0 ? cmnode[(size_t)p_at[(size_t)pn]] : ncm++;
-  std::vector<int64_t> cm_doff((size_t)ncm + 1, 0), cm_dofs((size_t)n);
-  for (int64_t x = 0; x < nu; ++x) {
-    int64_t d[4];
-    int sl[4];
-    cm_doff[(size_t)cmnode[(size_t)x] + 1] += node_dofs(x, d, sl);
-  }
-  for (int64_t y = 0; y < ncm; ++y) cm_doff[(size_t)y + 1] += cm_doff[(size_t)y];
-  {
-    std::vector<int64_t> f(cm_doff.begin(), cm_doff.end() - 1);
-    for (int64_t x = 0; x < nu; ++x) {  // velocity nodes come first: their components precede p
-      int64_t d[4];
-      int sl[4];
-      const int m = node_dofs(x, d, sl);
-      for (int j = 0; j < m; ++j) cm_dofs[(size_t)f[(size_t)cmnode[(size_t)x]]++] = d[j];
-    }
-  }
-  std::vector<int64_t> cadj_off((size_t)ncm + 1, 0), cadj;
-  {
-    std::vector<int64_t> ccoff((size_t)ncm + 1, 0), ccell;  // CM node -> cells
-    for (int64_t e = 0; e < nc; ++e)
-      for (int a = 0; a < ncn; ++a) ++ccoff[(size_t)cmnode[(size_t)cell_node(e, a)] + 1];
-    for (int64_t y = 0; y < ncm; ++y) ccoff[(size_t)y + 1] += ccoff[(size_t)y];
-    ccell.resize((size_t)ccoff[(size_t)ncm]);
-    std::vector<int64_t> f(ccoff.begin(), ccoff.end() - 1);
-    for (int64_t e = 0; e < nc; ++e)
-      for (int a = 0; a < ncn; ++a) ccell[(size_t)f[(size_t)cmnode[(size_t)cell_node(e, a)]]++] = e;
-    std::vector<int64_t> stamp((size_t)ncm, -1), buf;
-    for (int64_t y = 0; y < ncm; ++y) {
-      buf.clear();
-      buf.push_back(y);
-      stamp[(size_t)y] = y;
-      for (int64_t t = ccoff[(size_t)y]; t < ccoff[(size_t)y + 1]; ++t)
-        for (int a = 0; a < ncn; ++a) {
-          const int64_t z = cmnode[(size_t)cell_node(ccell[(size_t)t], a)];
-          if (stamp[(size_t)z] != y) { stamp[(size_t)z] = y; buf.push_back(z); }
-        }
-      std::sort(buf.begin(), buf.end());
-      cadj.insert(cadj.end(), buf.begin(), buf.end());
-      cadj_off[(size_t)y + 1] = (int64_t)cadj.size();
-    }
-  }
-  std::vector<int64_t> order;
-  gls::cuthill_mckee_nodes(ncm, cadj_off, cadj, cm_doff, cm_dofs, order);
-  if ((int64_t)order.size() != n) return set_err(GLS_EINVAL, "gls_ilu_attach: renumbering covers %lld of %lld DoFs", (long long)order.size(), (long long)n);
-  {
-    std::vector<char> seen((size_t)n, 0);
-    for (int64_t d : order)
-      if (d < 0 || d >= n || seen[(size_t)d]++) return set_err(GLS_EINVAL, "gls_ilu_attach: renumbering is not a permutation");
-  }
-  // subdomains (Ifpack's additive Schwarz with overlap 0, which the reference runs with one block per
-  // MPI rank): contiguous ranges of the cell order (space-filling: leaf order of the forest / Morton
-  // bricks), a DoF in the block of its lowest cell; couplings between blocks are dropped, each block
-  // is factored on its own, the blocks' triangular solves run side by side
-  const int nblk = I.block_dofs > 0 ? (int)std::min<int64_t>(std::max<int64_t>((n + I.block_dofs - 1) / I.block_dofs, 1), nc) : 1;
-  std::vector<int32_t> dblk((size_t)n, 0);
-  std::vector<int64_t> dnode_((size_t)n, 0);  // DoF -> unified node
-  for (int64_t x = 0; x < nu; ++x) {
-    int64_t d[4];
-    int sl[4];
-    const int m = node_dofs(x, d, sl);
-    for (int j = 0; j < m; ++j) dnode_[(size_t)d[j]] = x;
-  }
-  if (nblk > 1) {
-    std::vector<int32_t> nodeblk((size_t)nu, INT32_MAX);
-    for (int64_t e = 0; e < nc; ++e) {
-      const int32_t b = (int32_t)(e * nblk / nc);
-      for (int a = 0; a < ncn; ++a) {
-        int32_t &nb_ = nodeblk[(size_t)cell_node(e, a)];
-        nb_ = std::min(nb_, b);
-      }
-    }
-    for (int64_t d = 0; d < n; ++d) {
-      const int32_t b = nodeblk[(size_t)dnode_[(size_t)d]];
-      dblk[(size_t)d] = b == INT32_MAX ? 0 : b;
-    }
-  }
-  std::vector<int32_t> dcolor;  // multicolor: each DoF's color (its node's)
-  if (I.ordering == GLS_ILU_ORDER_MULTICOLOR) {
-    // multicolor order: a greedy distance-1 coloring of the node graph of the system matrix (nodes
-    // visited in Cuthill-McKee order); DoFs sorted by (color, node's first Cuthill-McKee position,
-    // position), so a node's DoFs stay consecutive. Same-colored nodes share no matrix entry: each
-    // color's diagonal block is block-diagonal by node, and the triangular solves' dependency chain
-    // is ~colors x DoFs per node. (Blocks only drop couplings here: the colors stay outermost.)
-    std::vector<int> c1((size_t)nu, -1), used;
-    int ncl = 0;
-    // visit order of the greedy coloring: Cuthill-McKee (smallest-last ordering gave 36 instead of 46 colors but
-    // 104 instead of 60 GMRES iterations, profiles/r03_ilu_coloring_ab.txt)
-    std::vector<int64_t> visit;
-    visit.reserve((size_t)nu);
-    std::vector<char> seen((size_t)nu, 0);
-    for (int64_t t = 0; t < n; ++t) {
-      const int64_t x = dnode_[(size_t)order[(size_t)t]];
-      if (!seen[(size_t)x]) {
-        seen[(size_t)x] = 1;
-        visit.push_back(x);
-      }
-    }
-    for (const int64_t x : visit) {
-      if (c1[(size_t)x] >= 0) continue;
-      for (int64_t u = n1off[(size_t)x]; u < n1off[(size_t)x + 1]; ++u) {
-        const int cy = c1[(size_t)n1[(size_t)u]];
-        if (cy >= 0) {
-          if ((int)used.size() <= cy) used.resize((size_t)cy + 1, -1);
-          used[(size_t)cy] = (int)x;
-        }
-      }
-      int col = 0;
-      while (col < (int)used.size() && used[(size_t)col] == (int)x) ++col;
-      c1[(size_t)x] = col;
-      ncl = std::max(ncl, col + 1);
-    }
-    I.n_order_colors = ncl;
-    std::vector<int64_t> npos((size_t)nu, INT64_MAX), pos((size_t)n);
-    for (int64_t t = 0; t < n; ++t) {
-      pos[(size_t)order[(size_t)t]] = t;
-      int64_t &np_ = npos[(size_t)dnode_[(size_t)order[(size_t)t]]];
-      np_ = std::min(np_, t);
-    }
-    dcolor.assign((size_t)n, 0);
-    for (int64_t d = 0; d < n; ++d) dcolor[(size_t)d] = c1[(size_t)dnode_[(size_t)d]];
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-      if (dcolor[(size_t)a] != dcolor[(size_t)b]) return dcolor[(size_t)a] < dcolor[(size_t)b];
-      const int64_t pa = npos[(size_t)dnode_[(size_t)a]], pb = npos[(size_t)dnode_[(size_t)b]];
-      if (pa != pb) return pa < pb;
-      return pos[(size_t)a] < pos[(size_t)b];
-    });
-  } else if (nblk > 1) {
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return dblk[(size_t)a] < dblk[(size_t)b]; });
-  }
-  std::vector<int32_t> newidx((size_t)n, -1), olddof((size_t)n);
-  for (int64_t r = 0; r < n; ++r) {
-    newidx[(size_t)order[(size_t)r]] = (int32_t)r;
-    olddof[(size_t)r] = (int32_t)order[(size_t)r];
-  }
-  // the system matrix's pattern in the new numbering, then its ILU(fill) pattern
-  std::vector<int64_t> arow((size_t)n + 1, 0);
-  std::vector<int32_t> acl;
-  std::vector<char> aclown;  // entry probed on this rank (pent / prow); else filled by the neighbours only
-  acl.reserve(acol.size());
-  {
-    std::vector<std::pair<int32_t, char>> rowbuf;
-    for (int64_t r = 0; r < n; ++r) {
-      const int64_t i = olddof[(size_t)r];
-      rowbuf.clear();
-      for (int64_t t = aoff[(size_t)i]; t < aoff[(size_t)i + 1]; ++t)
-        if (dblk[(size_t)acol[(size_t)t]] == dblk[(size_t)i]) rowbuf.push_back({newidx[(size_t)acol[(size_t)t]], aown[(size_t)t]});
-      std::sort(rowbuf.begin(), rowbuf.end());
-      for (const auto &e : rowbuf) {
-        acl.push_back(e.first);
-        aclown.push_back(e.second);
-      }
-      arow[(size_t)r + 1] = (int64_t)acl.size();
-    }
-  }
-  std::vector<int64_t> rowp;
-  std::vector<int32_t> col;
-  if (gls::iluk_pattern<int64_t>(n, arow.data(), acl.data(), fill, rowp, col) != GLS_OK)
-    return set_err(GLS_EINVAL, "gls_ilu_attach: ILU(%d) pattern", fill);
-  std::vector<int64_t> didx((size_t)n, -1);
-  for (int64_t r = 0; r < n; ++r) {
-    const auto b = col.begin() + rowp[(size_t)r], e = col.begin() + rowp[(size_t)r + 1];
-    const auto it = std::lower_bound(b, e, (int32_t)r);
-    if (it == e || *it != r) return set_err(GLS_EINVAL, "gls_ilu_attach: row %lld has no diagonal", (long long)r);
-    didx[(size_t)r] = (int64_t)(it - col.begin());
-  }
-  // multicolor solves: node groups (consecutive rows of one node), per color their range, per row
-  // the split of its entries into other colors / own node; valid while no entry couples two nodes of
-  // one color (fill 0; fill-in can create such entries: then rocSPARSE csrsv solves)
-  I.mc_solve = false;
-  I.mc_factor = false;
-  I.mc_compact = false;
-  std::vector<int64_t> mc_moff_h;  // position map offsets (empty: no map)
-  if (I.ordering == GLS_ILU_ORDER_MULTICOLOR) {
-    const int ncl = I.n_order_colors;
-    std::vector<int32_t> cstart((size_t)ncl + 2, (int32_t)n), grow, cg((size_t)ncl + 1, 0);
-    std::vector<int64_t> lsp((size_t)n), usp((size_t)n);
-    for (int64_t r = n - 1; r >= 0; --r) cstart[(size_t)dcolor[(size_t)olddof[(size_t)r]]] = (int32_t)r;
-    for (int c = ncl - 1; c >= 0; --c) cstart[(size_t)c] = std::min(cstart[(size_t)c], cstart[(size_t)c + 1]);
-    bool ok = true;
-    for (int64_t r = 0; r < n && ok; ++r) {
-      const int64_t x = dnode_[(size_t)olddof[(size_t)r]];
-      if (r == 0 || x != dnode_[(size_t)olddof[(size_t)r - 1]]) grow.push_back((int32_t)r);
-      if (r + 1 - grow.back() > gls::kMaxGroupRows) ok = false;
-      const int cr = dcolor[(size_t)olddof[(size_t)r]];
-      int64_t e = rowp[(size_t)r];
-      while (e < rowp[(size_t)r + 1] && col[(size_t)e] < cstart[(size_t)cr]) ++e;
-      lsp[(size_t)r] = e;
-      while (e < rowp[(size_t)r + 1] && col[(size_t)e] < cstart[(size_t)cr + 1]) {
-        if (dnode_[(size_t)olddof[(size_t)col[(size_t)e]]] != x) ok = false;  // same color, other node
-        ++e;
-      }
-      usp[(size_t)r] = e;
-    }
-    if (ok) {
-      grow.push_back((int32_t)n);
-      for (int c = 0, g = 0; c <= ncl; ++c) {
-        while (g + 1 < (int)grow.size() && grow[(size_t)g] < cstart[(size_t)c]) ++g;
-        cg[(size_t)c] = c == ncl ? (int)grow.size() - 1 : g;
-      }
-      GLS_TRY(I.mc_grow.upload(grow.data(), grow.size()));
-      GLS_TRY(I.mc_lsp.upload(lsp.data(), lsp.size()));
-      GLS_TRY(I.mc_usp.upload(usp.data(), usp.size()));
-      {
-        const size_t ng = grow.size() - 1;
-        std::vector<int64_t> desc(ng * gls::kGroupDesc, 0);
-        for (size_t g = 0; g < ng; ++g) {
-          int64_t *d = &desc[g * gls::kGroupDesc];
-          const int32_t r0 = grow[g], nr = grow[g + 1] - r0;
-          d[0] = r0;
-          d[1] = nr;
-          d[2] = rowp[(size_t)r0];
-          d[3] = rowp[(size_t)(r0 + nr)];
-          for (int t = 1; t < 4; ++t) d[3 + t] = t < nr ? rowp[(size_t)(r0 + t)] : INT64_MAX;
-          for (int t = 0; t < nr; ++t) {
-            d[8 + t] = lsp[(size_t)(r0 + t)];
-            d[12 + t] = usp[(size_t)(r0 + t)];
-            d[16 + t] = didx[(size_t)(r0 + t)];
-            d[20 + t] = rowp[(size_t)(r0 + t) + 1];
-          }
-        }
-        GLS_TRY(I.mc_desc.upload(desc.data(), desc.size()));
-      }
-      I.mc_cg = cg;
-      I.mc_solve = true;
-      int64_t maxrow = 0;
-      for (int64_t r = 0; r < n; ++r) maxrow = std::max(maxrow, rowp[(size_t)r + 1] - rowp[(size_t)r]);
-      I.mc_factor = maxrow <= gls::kIluMaxRow && rowp.back() < (int64_t(1) << 35) && !std::getenv("GLS_ILU_ROCSPARSE_FACTOR");
-      I.mc_compact = maxrow <= gls::kIluCompactRow;
-      if (I.mc_factor) GLS_TRY(I.rdiag.alloc((size_t)n));
-      if (I.mc_factor) {  // the position map (uint16 per entry), when it fits a quarter of free memory
-        mc_moff_h.assign((size_t)n + 1, 0);
-        for (int64_t r = 0; r < n; ++r) {
-          int64_t m = 0;
-          for (int64_t e = rowp[(size_t)r]; e < lsp[(size_t)r]; ++e) {
-            const int32_t k = col[(size_t)e];
-            m += (rowp[(size_t)k + 1] - didx[(size_t)k] - 1 + 3) & ~3;  // segments padded to quads
-          }
-          mc_moff_h[(size_t)r + 1] = mc_moff_h[(size_t)r] + m;
-        }
-        size_t fr = 0, tot = 0;
-        const char *me = std::getenv("GLS_ILU_FACTOR_MAP");
-        if ((me && std::atoi(me) == 0) || hipMemGetInfo(&fr, &tot) != hipSuccess ||
-            (double)mc_moff_h[(size_t)n] * 2.0 > 0.25 * (double)fr)
-          mc_moff_h.clear();
-      }
-      // per color and direction: one wavefront per node group while a group's other-color entries
-      // fit a few passes of 64 lanes, else four (long rows: the late colors' L parts, the early
-      // colors' U parts)
-      I.mc_wl.assign((size_t)ncl, 1);
-      I.mc_wu.assign((size_t)ncl, 1);
-      for (int c = 0; c < ncl; ++c) {
-        const int32_t ra = grow[(size_t)cg[(size_t)c]], rb = grow[(size_t)cg[(size_t)c + 1]];
-        const int ng = cg[(size_t)c + 1] - cg[(size_t)c];
-        int64_t nlo = 0, nup = 0;
-        for (int32_t r = ra; r < rb; ++r) {
-          nlo += lsp[(size_t)r] - rowp[(size_t)r];
-          nup += rowp[(size_t)r + 1] - usp[(size_t)r];
-        }
-        I.mc_wl[(size_t)c] = (uint8_t)(ng && nlo > 256 * (int64_t)ng ? 4 : 1);
-        I.mc_wu[(size_t)c] = (uint8_t)(ng && nup > 256 * (int64_t)ng ? 4 : 1);
-      }
-    }
-  }
-  // probes: one per (color, slot); every entry of the system matrix is read from the probe of its
-  // column DoF (entry position in the ILU pattern, row's original DoF)
-  const int nprobe = ncol * (dim + 1);
-  std::vector<int> dslot((size_t)n, 0);
-  std::vector<int64_t> dnode((size_t)n, 0);
-  for (int64_t x = 0; x < nu; ++x) {
-    int64_t d[4];
-    int sl[4];
-    const int m = node_dofs(x, d, sl);
-    for (int j = 0; j < m; ++j) { dslot[(size_t)d[j]] = sl[j]; dnode[(size_t)d[j]] = x; }
-  }
-  auto probe_of = [&](int64_t d) { return color[(size_t)dnode[(size_t)d]] * (dim + 1) + dslot[(size_t)d]; };
-  std::vector<int64_t> pdoff((size_t)nprobe + 1, 0), peoff((size_t)nprobe + 1, 0);
-  for (int64_t d = 0; d < n; ++d) ++pdoff[(size_t)probe_of(d) + 1];
-  for (int64_t r = 0; r < n; ++r)
-    for (int64_t t = arow[(size_t)r]; t < arow[(size_t)r + 1]; ++t)
-      if (aclown[(size_t)t]) ++peoff[(size_t)probe_of(olddof[(size_t)acl[(size_t)t]]) + 1];
-  for (int p = 0; p < nprobe; ++p) {
-    pdoff[(size_t)p + 1] += pdoff[(size_t)p];
-    peoff[(size_t)p + 1] += peoff[(size_t)p];
-  }
-  std::vector<int32_t> pdofs((size_t)pdoff[(size_t)nprobe]), prow((size_t)peoff[(size_t)nprobe]);
-  std::vector<int64_t> pent(prow.size());
-  {
-    std::vector<int64_t> f1(pdoff.begin(), pdoff.end() - 1), f2(peoff.begin(), peoff.end() - 1);
-    // (complete rows: the unconstrained ghost DoFs are probed too)
-    for (int64_t d = 0; d < n; ++d)
-      pdofs[(size_t)f1[(size_t)probe_of(d)]++] = ghost(d) && !(cmpl && !fcons[(size_t)d]) ? -1 : (int32_t)d;
-    for (int64_t r = 0; r < n; ++r) {
-      int64_t pos = rowp[(size_t)r];
-      for (int64_t t = arow[(size_t)r]; t < arow[(size_t)r + 1]; ++t) {
-        while (col[(size_t)pos] < acl[(size_t)t]) ++pos;  // both rows sorted; A's pattern is a subset
-        if (!aclown[(size_t)t]) continue;
-        const int64_t k = f2[(size_t)probe_of(olddof[(size_t)acl[(size_t)t]])]++;
-        pent[(size_t)k] = pos;
-        prow[(size_t)k] = olddof[(size_t)r];  // the probe result is indexed by the original DoF
-      }
-    }
-  }
-  I.release();
-  GLS_TRY(I.rowp.upload(rowp.data(), rowp.size()));
-  GLS_TRY(I.col.upload(col.data(), col.size()));
-  GLS_TRY(I.didx.upload(didx.data(), didx.size()));
-  GLS_TRY(I.perm.upload(newidx.data(), newidx.size()));
-  I.mc_map.release();
-  I.mc_moff.release();
-  if (!mc_moff_h.empty()) {
-    GLS_TRY(I.mc_moff.upload(mc_moff_h.data(), mc_moff_h.size()));
-    GLS_TRY(I.mc_map.alloc((size_t)mc_moff_h.back() + 256));  // + the clamped index of empty stages
-    HIP_TRY(gls::ilu_mc_factor_map(n, I.rowp.p, I.col.p, I.mc_lsp.p, I.didx.p, I.mc_moff.p, I.mc_map.p, c->stream));
-  }
-  // ghost DoFs are not probed (identity rows): drop them from the unit lists, remember their diagonals
-  {
-    std::vector<int32_t> pd2;
-    std::vector<int64_t> pdoff2((size_t)nprobe + 1, 0);
-    for (int p = 0; p < nprobe; ++p) {
-      for (int64_t t = pdoff[(size_t)p]; t < pdoff[(size_t)p + 1]; ++t)
-        if (pdofs[(size_t)t] >= 0) pd2.push_back(pdofs[(size_t)t]);
-      pdoff2[(size_t)p + 1] = (int64_t)pd2.size();
-    }
-    pdofs.swap(pd2);
-    pdoff.swap(pdoff2);
-    std::vector<int64_t> gd;
-    for (int64_t r = 0; r < n; ++r)
-      if (ghost(olddof[(size_t)r])) gd.push_back(didx[(size_t)r]);
-    GLS_TRY(I.ghost_diag.upload(gd.data(), gd.size()));
-  }
-  // the neighbours' entries: per round, each CSR entry's send_buf slots in (round, neighbour, slot) order
-  {
-    std::vector<std::pair<int64_t, int64_t>> key;  // (round * nnz + entry, record) sorted stably
-    const int64_t nnz = (int64_t)col.size();
-    for (size_t q = 0; q < remote.size(); ++q) {
-      const auto &e = remote[q];
-      if (dblk[(size_t)e.i] != dblk[(size_t)e.j]) continue;
-      const int32_t r = newidx[(size_t)e.i], cj = newidx[(size_t)e.j];
-      const auto b = col.begin() + rowp[(size_t)r], en = col.begin() + rowp[(size_t)r + 1];
-      const auto it = std::lower_bound(b, en, cj);
-      if (it == en || *it != cj) return set_err(GLS_EINVAL, "gls_ilu_attach: a neighbour's entry is not in the pattern");
-      key.push_back({(int64_t)e.round * nnz + (int64_t)(it - col.begin()), (int64_t)q});
-    }
-    std::stable_sort(key.begin(), key.end(), [](const std::pair<int64_t, int64_t> &a, const std::pair<int64_t, int64_t> &b) {
-      return a.first < b.first;
-    });
-    std::vector<int64_t> ru;
-    std::vector<int32_t> ruoff{0}, rslot;
-    std::vector<int64_t> rr((size_t)std::max(n_rounds, 0) + 1, 0);
-    for (size_t t = 0; t < key.size(); ++t) {
-      if (t == 0 || key[t].first != key[t - 1].first) {
-        if (t) ruoff.push_back((int32_t)rslot.size());
-        ru.push_back(key[t].first % nnz);
-        ++rr[(size_t)(key[t].first / nnz) + 1];
-      }
-      rslot.push_back(remote[(size_t)key[t].second].slot);
-    }
-    if (!key.empty()) ruoff.push_back((int32_t)rslot.size());
-    for (int p = 0; p < n_rounds; ++p) rr[(size_t)p + 1] += rr[(size_t)p];
-    ru.push_back(0);  // (padding: no zero-sized device buffers)
-    rslot.push_back(0);
-    GLS_TRY(I.ru.upload(ru.data(), ru.size()));
-    GLS_TRY(I.ruoff.upload(ruoff.data(), ruoff.size()));
-    GLS_TRY(I.rslot.upload(rslot.data(), rslot.size()));
-    I.rr = rr;
-    I.complete = cmpl;
-    I.n_rounds = n_rounds;
-  }
-  GLS_TRY(I.pdofs.upload(pdofs.data(), pdofs.size()));
-  GLS_TRY(I.pent.upload(pent.data(), pent.size()));
-  GLS_TRY(I.prow.upload(prow.data(), prow.size()));
-  {  // probe of every unit DoF and every extracted entry (batched probing)
-    std::vector<int32_t> pdp(std::max<size_t>(pdofs.size(), 1)), pep(std::max<size_t>(pent.size(), 1));
-    for (int p = 0; p < nprobe; ++p) {
-      for (int64_t t = pdoff[(size_t)p]; t < pdoff[(size_t)p + 1]; ++t) pdp[(size_t)t] = p;
-      for (int64_t t = peoff[(size_t)p]; t < peoff[(size_t)p + 1]; ++t) pep[(size_t)t] = p;
-    }
-    GLS_TRY(I.pdpid.upload(pdp.data(), pdp.size()));
-    GLS_TRY(I.pepid.upload(pep.data(), pep.size()));
-  }
-  GLS_TRY(I.val.alloc(col.size() + 256));  // + the factorization's whole-quad loads past a row's end
-  HIP_TRY(hipMemset(I.val.p, 0, col.size() * sizeof(double)));
-  GLS_TRY(I.vbuf.alloc((size_t)n));
-  GLS_TRY(I.ybuf.alloc((size_t)n));
-  GLS_TRY(I.tbuf.alloc((size_t)n));
-  I.pdoff = pdoff;
-  I.woff.clear();  // new probes: their activity is recorded again
-  I.peoff = peoff;
-  I.n_probes = nprobe;
-  I.nnz = (int64_t)col.size();
-  I.nnz_a = (int64_t)acl.size();
-  I.fill = fill;
-  I.n_blocks = nblk;
-  I.athresh = athresh;
-  I.rthresh = rthresh;
-  // the multicolor kernels factor and solve: no rocSPARSE state (its csrilu0 / csrsv analyses were a setup cost of
-  // ~0.9 s at 1.7 M DoFs, a radix sort each, for solves that never ran); past 2^31 entries they are the only route
-  // (rocSPARSE takes 32-bit CSR)
-  if (I.nnz >= INT32_MAX || (I.mc_factor && I.mc_solve)) {
-    if (!I.mc_factor || !I.mc_solve)
-      return set_err(GLS_EINVAL, "gls_ilu_attach: %lld entries (> 2^31): the multicolor order with fill 0 is needed",
-                     (long long)I.nnz);
-    I.boost_tol = athresh > 0 ? athresh : 1e-300;  // as below, read by the multicolor factorization
-    I.boost_val = athresh > 0 ? athresh : 1e-12;
-    I.valid = false;
-    I.on = true;
-    return GLS_OK;
-  }
-  {
-    std::vector<int32_t> rp32(rowp.begin(), rowp.end());
-    GLS_TRY(I.rowp32.upload(rp32.data(), rp32.size()));
-  }
-  RS_TRY(rocsparse_create_handle(&I.h));
-  RS_TRY(rocsparse_set_stream(I.h, c->stream));
-  RS_TRY(rocsparse_create_mat_descr(&I.dA));
-  RS_TRY(rocsparse_create_mat_descr(&I.dL));
-  RS_TRY(rocsparse_set_mat_fill_mode(I.dL, rocsparse_fill_mode_lower));
-  RS_TRY(rocsparse_set_mat_diag_type(I.dL, rocsparse_diag_type_unit));
-  RS_TRY(rocsparse_create_mat_descr(&I.dU));
-  RS_TRY(rocsparse_set_mat_fill_mode(I.dU, rocsparse_fill_mode_upper));
-  RS_TRY(rocsparse_set_mat_diag_type(I.dU, rocsparse_diag_type_non_unit));
-  RS_TRY(rocsparse_create_mat_info(&I.info));
-  const rocsparse_int m = (rocsparse_int)n, nnz = (rocsparse_int)I.nnz;
-  size_t b0 = 0, b1 = 0, b2 = 0;
-  RS_TRY(rocsparse_dcsrilu0_buffer_size(I.h, m, nnz, I.dA, I.val.p, I.rowp32.p, I.col.p, I.info, &b0));
-  RS_TRY(rocsparse_dcsrsv_buffer_size(I.h, rocsparse_operation_none, m, nnz, I.dL, I.val.p, I.rowp32.p, I.col.p, I.info, &b1));
-  RS_TRY(rocsparse_dcsrsv_buffer_size(I.h, rocsparse_operation_none, m, nnz, I.dU, I.val.p, I.rowp32.p, I.col.p, I.info, &b2));
-  GLS_TRY(I.work.alloc(std::max(std::max(b0, b1), std::max(b2, (size_t)16))));
-  RS_TRY(rocsparse_dcsrilu0_analysis(I.h, m, nnz, I.dA, I.val.p, I.rowp32.p, I.col.p, I.info, rocsparse_analysis_policy_reuse,
-                                     rocsparse_solve_policy_auto, I.work.p));
-  RS_TRY(rocsparse_dcsrsv_analysis(I.h, rocsparse_operation_none, m, nnz, I.dL, I.val.p, I.rowp32.p, I.col.p, I.info,
-                                   rocsparse_analysis_policy_reuse, rocsparse_solve_policy_auto, I.work.p));
-  RS_TRY(rocsparse_dcsrsv_analysis(I.h, rocsparse_operation_none, m, nnz, I.dU, I.val.p, I.rowp32.p, I.col.p, I.info,
-                                   rocsparse_analysis_policy_reuse, rocsparse_solve_policy_auto, I.work.p));
-  // pivots that end below athresh in magnitude are boosted to athresh (enclosed-flow pressure mode)
-  // (rocsparse stores the two pointers and reads them at every csrilu0: they must outlive this call;
-  // stack locals here gave the first factorization whatever the stack later held)
-  I.boost_tol = athresh > 0 ? athresh : 1e-300;
-  I.boost_val = athresh > 0 ? athresh : 1e-12;
-  RS_TRY(rocsparse_dcsrilu0_numeric_boost(I.h, I.info, 1, &I.boost_tol, &I.boost_val));
-  I.on = true;
-  I.valid = false;
-  if (std::getenv("GLS_ILU_VERBOSE"))
-    std::printf("ilu attach: n %lld fill %d blocks %d ordering %s (%d colors%s) nnz(A) %lld nnz(ILU) %lld probe colors "
-                "%d probes %d\n", (long long)n, fill, nblk, I.ordering == GLS_ILU_ORDER_CM ? "cuthill-mckee" : "multicolor",
-                I.n_order_colors, I.mc_solve ? ", color solves" : "", (long long)I.nnz_a, (long long)I.nnz, ncol, nprobe);
-  return GLS_OK;
-}
-extern "C" int gls_ilu_set_options(gls_ctx *c, int ordering, int64_t block_dofs) {
-  GLS_TRY(check_ctx(c));
-  if (block_dofs < 0) return set_err(GLS_EINVAL, "gls_ilu_set_options: negative block size");
-  if (ordering != GLS_ILU_ORDER_CM && ordering != GLS_ILU_ORDER_MULTICOLOR)
-    return set_err(GLS_EINVAL, "gls_ilu_set_options: ordering %d", ordering);
-  c->ilu.block_dofs = block_dofs;
-  c->ilu.ordering = ordering;
-  return GLS_OK;
-}
-extern "C" int gls_ilu_detach(gls_ctx *c) {
-  GLS_TRY(check_ctx(c));
-  c->ilu.on = false;
-  c->ilu.probe_only = false;
-  c->ilu.release();
-  return GLS_OK;
-}
-// the probed (unfactored, unperturbed) operator matrix, for tests: host CSR arrays of gls_ilu_info's nnz
-extern "C" int gls_ilu_matrix(gls_ctx *c, int32_t *rowp, int32_t *col, double *val) {
-  GLS_TRY(check_ctx(c));
-  auto &I = c->ilu;
-  if (!I.on) return set_err(GLS_EINVAL, "no ILU attached");
-  GLS_TRY(ilu_probe(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  // renumbered CSR on the device; returned in the context's DoF numbering
-  const int64_t n = c->n_dofs;
-  if (I.nnz >= INT32_MAX) return set_err(GLS_EINVAL, "gls_ilu_matrix: %lld entries do not fit its 32-bit CSR", (long long)I.nnz);
-  std::vector<int64_t> rp((size_t)n + 1);
-  std::vector<int32_t> cl((size_t)I.nnz), pm((size_t)n);
-  std::vector<double> vl((size_t)I.nnz);
-  HIP_TRY(hipMemcpy(rp.data(), I.rowp.p, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(cl.data(), I.col.p, sizeof(int32_t) * cl.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(vl.data(), I.val.p, sizeof(double) * vl.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(pm.data(), I.perm.p, sizeof(int32_t) * pm.size(), hipMemcpyDeviceToHost));
-  std::vector<int32_t> old((size_t)n);
-  for (int64_t i = 0; i < n; ++i) old[(size_t)pm[(size_t)i]] = (int32_t)i;
-  std::vector<std::vector<std::pair<int32_t, double>>> rows((size_t)n);
-  for (int64_t r = 0; r < n; ++r)
-    for (int64_t e = rp[(size_t)r]; e < rp[(size_t)r + 1]; ++e) rows[(size_t)old[(size_t)r]].push_back({old[(size_t)cl[(size_t)e]], vl[(size_t)e]});
-  int64_t k = 0;
-  if (rowp) rowp[0] = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    std::sort(rows[(size_t)i].begin(), rows[(size_t)i].end());
-    for (auto &pr : rows[(size_t)i]) {
-      if (col) col[k] = pr.first;
-      if (val) val[k] = pr.second;
-      ++k;
-    }
-    if (rowp) rowp[i + 1] = (int32_t)k;
-  }
-  I.valid = false;  // the values now hold the unfactored matrix
-  return GLS_OK;
-}
-// the factored ILU(fill) (after the diagonal perturbation) in the factorization's numbering, for
-// tests: perm[dof] = its row; rowp / col / val of gls_ilu_info's nnz entries (unit-diagonal L below
-// the diagonal, U on and above it, as rocSPARSE csrilu0 stores them)
-extern "C" int gls_ilu_factors(gls_ctx *c, int32_t *perm, int32_t *rowp, int32_t *col, double *val) {
-  GLS_TRY(check_ctx(c));
-  auto &I = c->ilu;
-  if (!I.on) return set_err(GLS_EINVAL, "no ILU attached");
-  GLS_TRY(ensure_diag(c));
-  GLS_TRY(ensure_ilu(c));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (perm) HIP_TRY(hipMemcpy(perm, I.perm.p, sizeof(int32_t) * (size_t)c->n_dofs, hipMemcpyDeviceToHost));
-  if (I.nnz >= INT32_MAX) return set_err(GLS_EINVAL, "gls_ilu_factors: %lld entries do not fit its 32-bit CSR", (long long)I.nnz);
-  if (rowp) {
-    std::vector<int64_t> rp((size_t)c->n_dofs + 1);
-    HIP_TRY(hipMemcpy(rp.data(), I.rowp.p, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < rp.size(); ++i) rowp[i] = (int32_t)rp[i];
-  }
-  if (col) HIP_TRY(hipMemcpy(col, I.col.p, sizeof(int32_t) * (size_t)I.nnz, hipMemcpyDeviceToHost));
-  if (val) HIP_TRY(hipMemcpy(val, I.val.p, sizeof(double) * (size_t)I.nnz, hipMemcpyDeviceToHost));
-  return GLS_OK;
-}
-extern "C" int gls_ilu_info(const gls_ctx *c, int64_t *nnz, int *n_probes) {
-  if (!c) return set_err(GLS_EINVAL, "null context");
-  if (nnz) *nnz = c->ilu.nnz;
-  if (n_probes) *n_probes = c->ilu.n_probes;
-  return c->ilu.on ? GLS_OK : set_err(GLS_EINVAL, "no ILU attached");
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// In-library RCCL over xGMI (the reference's Trilinos ghost import / compress(add) and
-// MPI_Allreduce, gls_navier_stokes.cc:186-202, 774-776): one communicator per process, shared by
-// the contexts of every multigrid level; exchanges and reductions are enqueued on the context
-// stream (RCCL orders them with the pack / unpack kernels), so no exchange blocks the host.
-// ---------------------------------------------------------------------------------------------
-struct gls_rccl {
-  ncclComm_t comm = nullptr;
-  int rank = 0, world = 1;
-};
-namespace {
-int rccl_exchange(void *user, int phase) { return rccl_exchange_on(static_cast<gls_ctx *>(user), phase, static_cast<gls_ctx *>(user)->stream); }
-int rccl_allreduce(void *user, double *buf, int n) {
-  gls_ctx *c = static_cast<gls_ctx *>(user);
-  return ncclAllReduce(buf, buf, (size_t)n, ncclDouble, ncclSum, c->dist.comm, c->stream) == ncclSuccess ? 0 : -1;
-}
-int rccl_exchange_on(gls_ctx *c, int phase, hipStream_t stream) {
-  auto &D = c->dist;
-  // phase 0 (import): send send_buf segments (owned nodes others ghost), receive into recv_buf;
-  // phase 1 (export-add): the reverse (ghost partial sums back to their owners)
-  double *sb = phase == 0 ? D.send_buf : D.recv_buf, *rb = phase == 0 ? D.recv_buf : D.send_buf;
-  const std::vector<int64_t> &so = phase == 0 ? D.soff : D.roff, &ro = phase == 0 ? D.roff : D.soff;
-  if (ncclGroupStart() != ncclSuccess) return -1;
-  for (size_t i = 0; i < D.nbrs.size(); ++i) {
-    const int w = D.width;
-    const size_t ns = (size_t)(w * (so[i + 1] - so[i])), nr = (size_t)(w * (ro[i + 1] - ro[i]));
-    if (ns && ncclSend(sb + w * so[i], ns, ncclDouble, D.nbrs[i], D.comm, stream) != ncclSuccess) return -1;
-    if (nr && ncclRecv(rb + w * ro[i], nr, ncclDouble, D.nbrs[i], D.comm, stream) != ncclSuccess) return -1;
-  }
-  return ncclGroupEnd() == ncclSuccess ? 0 : -1;
-}
-}  // namespace
-
-extern "C" int gls_rccl_unique_id(unsigned char *id_out) {
-  if (!id_out) return set_err(GLS_EINVAL, "gls_rccl_unique_id: null output");
-  ncclUniqueId id;
-  const ncclResult_t r = ncclGetUniqueId(&id);
-  if (r != ncclSuccess) return set_err(GLS_ECOMM, "ncclGetUniqueId: %s", ncclGetErrorString(r));
-  static_assert(sizeof(id) == GLS_RCCL_ID_BYTES, "ncclUniqueId size");
-  std::memcpy(id_out, &id, sizeof(id));
-  return GLS_OK;
-}
-extern "C" int gls_rccl_create(const unsigned char *id_in, int rank, int world, gls_rccl **out) {
-  if (!id_in || !out || world < 1 || rank < 0 || rank >= world) return set_err(GLS_EINVAL, "gls_rccl_create: bad arguments");
-  ncclUniqueId id;
-  std::memcpy(&id, id_in, sizeof(id));
-  auto r = std::make_unique<gls_rccl>();
-  const ncclResult_t e = ncclCommInitRank(&r->comm, world, id, rank);
-  if (e != ncclSuccess) return set_err(GLS_ECOMM, "ncclCommInitRank(%d of %d): %s", rank, world, ncclGetErrorString(e));
-  r->rank = rank;
-  r->world = world;
-  *out = r.release();
-  return GLS_OK;
-}
-// the communicator's own view (ncclCommUserRank / ncclCommCount): what bench.py reports as rccl_ranks
-extern "C" int gls_rccl_info(const gls_rccl *r, int *rank, int *world) {
-  if (!r || !r->comm) return set_err(GLS_EINVAL, "gls_rccl_info: no communicator");
-  int rk = -1, n = 0;
-  if (ncclCommUserRank(r->comm, &rk) != ncclSuccess || ncclCommCount(r->comm, &n) != ncclSuccess)
-    return set_err(GLS_ECOMM, "gls_rccl_info: ncclCommUserRank / ncclCommCount failed");
-  if (rank) *rank = rk;
-  if (world) *world = n;
-  return GLS_OK;
-}
-extern "C" int gls_rccl_destroy(gls_rccl *r) {
-  if (!r) return GLS_OK;
-  if (r->comm) (void)ncclCommDestroy(r->comm);
-  delete r;
-  return GLS_OK;
-}
-extern "C" int gls_dist_attach_rccl(gls_ctx *c, gls_rccl *r, int64_t n_owned_nodes, int n_nbrs, const int *nbr_ranks,
-                                    const int64_t *send_offsets, const int32_t *send_nodes, const int64_t *recv_offsets,
-                                    const int32_t *recv_nodes) {
-  GLS_TRY(check_ctx(c));
-  if (!r || !r->comm || n_nbrs < 0 || (n_nbrs > 0 && (!nbr_ranks || !send_offsets || !recv_offsets)))
-    return set_err(GLS_EINVAL, "gls_dist_attach_rccl: bad arguments");
-  auto &D = c->dist;
-  const int64_t ns = n_nbrs ? send_offsets[n_nbrs] : 0, nr = n_nbrs ? recv_offsets[n_nbrs] : 0;
-  for (int i = 0; i < n_nbrs; ++i)
-    if (nbr_ranks[i] < 0 || nbr_ranks[i] >= r->world || nbr_ranks[i] == r->rank)
-      return set_err(GLS_EINVAL, "gls_dist_attach_rccl: neighbour rank %d", nbr_ranks[i]);
-  GLS_TRY(D.own_send.alloc((size_t)std::max<int64_t>(4 * ns, 1)));
-  GLS_TRY(D.own_recv.alloc((size_t)std::max<int64_t>(4 * nr, 1)));
-  GLS_TRY(D.own_red.alloc(256));
-  GLS_TRY(gls_dist_attach(c, n_owned_nodes, n_nbrs, send_offsets, send_nodes, recv_offsets, recv_nodes, D.own_send.p,
-                          D.own_recv.p, D.own_red.p, rccl_exchange, rccl_allreduce, c));
-  D.comm = r->comm;
-  if (!D.xstream) {
-    HIP_TRY(hipStreamCreateWithFlags(&D.xstream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&D.ev_ready, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&D.ev_done, hipEventDisableTiming));
-  }
-  D.nbrs.assign(nbr_ranks, nbr_ranks + n_nbrs);
-  D.soff.assign(send_offsets, send_offsets + n_nbrs + 1);
-  D.roff.assign(recv_offsets, recv_offsets + n_nbrs + 1);
-  if (n_nbrs == 0) {
-    D.soff.assign(1, 0);
-    D.roff.assign(1, 0);
-  }
-  return GLS_OK;
-}
-
-extern "C" int gls_dist_attach_dofs_rccl(gls_ctx *c, gls_rccl *r, int64_t n_owned_vnodes, int64_t n_owned_pnodes,
-                                         int n_nbrs, const int *nbr_ranks, const int64_t *send_offsets,
-                                         const int32_t *send_dofs, const int64_t *recv_offsets, const int32_t *recv_dofs) {
-  GLS_TRY(check_ctx(c));
-  if (!r || !r->comm || n_nbrs < 0 || (n_nbrs > 0 && (!nbr_ranks || !send_offsets || !recv_offsets)))
-    return set_err(GLS_EINVAL, "gls_dist_attach_dofs_rccl: bad arguments");
-  auto &D = c->dist;
-  const int64_t ns = n_nbrs ? send_offsets[n_nbrs] : 0, nr = n_nbrs ? recv_offsets[n_nbrs] : 0;
-  for (int i = 0; i < n_nbrs; ++i)
-    if (nbr_ranks[i] < 0 || nbr_ranks[i] >= r->world || nbr_ranks[i] == r->rank)
-      return set_err(GLS_EINVAL, "gls_dist_attach_dofs_rccl: neighbour rank %d", nbr_ranks[i]);
-  GLS_TRY(D.own_send.alloc((size_t)std::max<int64_t>(ns, 1)));
-  GLS_TRY(D.own_recv.alloc((size_t)std::max<int64_t>(nr, 1)));
-  GLS_TRY(D.own_red.alloc(256));
-  GLS_TRY(gls_dist_attach_dofs(c, n_owned_vnodes, n_owned_pnodes, n_nbrs, send_offsets, send_dofs, recv_offsets, recv_dofs,
-                               D.own_send.p, D.own_recv.p, D.own_red.p, rccl_exchange, rccl_allreduce, c));
-  D.comm = r->comm;
-  D.nbrs.assign(nbr_ranks, nbr_ranks + n_nbrs);
-  D.soff.assign(send_offsets, send_offsets + n_nbrs + 1);
-  D.roff.assign(recv_offsets, recv_offsets + n_nbrs + 1);
-  if (n_nbrs == 0) {
-    D.soff.assign(1, 0);
-    D.roff.assign(1, 0);
-  }
-  return GLS_OK;
-}

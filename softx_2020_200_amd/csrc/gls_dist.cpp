@@ -22,8 +22,7 @@
 #include <vector>
 
 #include "../../include/gls_native.h"
-
-int gls_internal_set_err(int code, const char *msg);
+#include "gls_error.hpp"
 
 struct gls_part {
   int64_t cell_begin = 0, cell_end = 0, n_owned = 0, n_local = 0;

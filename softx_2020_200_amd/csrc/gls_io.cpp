@@ -28,8 +28,7 @@
 #include <vector>
 
 #include "../../include/gls_native.h"
-
-int gls_io_set_error(int code, const char *fmt, ...);  // gls_api.cpp (shared last-error buffer)
+#include "gls_error.hpp"
 
 namespace {
 

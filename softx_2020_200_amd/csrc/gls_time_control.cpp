@@ -5,8 +5,7 @@
 #include <cmath>
 
 #include "../../include/gls_native.h"
-
-int gls_internal_set_err(int code, const char *msg);  // gls_api.cpp
+#include "gls_error.hpp"
 
 struct gls_time_control {
   gls_time_control_params prm;

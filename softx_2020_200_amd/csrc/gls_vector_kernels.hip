@@ -755,7 +755,7 @@ hipError_t vec_set_indexed(double *y, const int64_t *idx, const double *vals, in
 
 }  // namespace gls
 
-// ---- assembled-ILU preconditioner helpers (gls_api.cpp ilu_*): probe vectors and value extraction
+// ---- assembled-ILU preconditioner helpers (gls_ilu.cpp ilu_*): probe vectors and value extraction
 namespace gls {
 namespace {
 template <typename I>

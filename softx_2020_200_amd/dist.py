@@ -1,7 +1,7 @@
 """Multi-GPU driver glue: one process per GPU, torch.distributed ("nccl" = RCCL over xGMI).
 
 The partition plan and every kernel (pack/unpack, operators, GMRES, Newton) live in
-libgls_native.so (csrc/gls_dist.cpp, gls_api.cpp). This module only
+libgls_native.so (csrc/gls_dist.cpp, gls_api.cpp, gls_rccl.cpp). This module only
   * calls gls_part_* to get the rank-local mesh and exchange lists,
   * owns the device exchange buffers (4 doubles per exchanged node: u, v, w, p),
   * implements the two callbacks the C++ side calls: ghost exchange (grouped point-to-point

@@ -31,7 +31,7 @@ EXPORTS = [
     "gls_mesh_hyper_cube", "gls_timing_reset", "gls_timing_get", "gls_timing_enable", "gls_uses_brick_kernels",
     "gls_part_create", "gls_part_sizes", "gls_part_get", "gls_part_destroy", "gls_dist_attach", "gls_dist_import", "gls_rccl_unique_id", "gls_rccl_create", "gls_rccl_destroy", "gls_rccl_info", "gls_mg_smoother_apply", "gls_mg_attach_replica",
     "gls_dist_attach_rccl",
-    "gls_mg_attach", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
+    "gls_mg_attach", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_ilu_plan", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
     "gls_mg_residual_restrict", "gls_mg_prolong_smooth",
     "gls_prm_parse", "gls_prm_get", "gls_prm_n_entries", "gls_prm_entry", "gls_prm_destroy",
     "gls_expr_create", "gls_expr_n_components", "gls_expr_eval", "gls_expr_destroy",
@@ -1385,6 +1385,37 @@ def iluk_pattern(A, fill):
     check(L.gls_iluk_pattern(n, rowp.ctypes.data, col.ctypes.data, int(fill), orow.ctypes.data, ocol.ctypes.data,
                              olev.ctypes.data, nnz.value, C.byref(nnz)), "gls_iluk_pattern")
     return orow, ocol, olev
+
+
+def ilu_plan(dim, k, kp, n_vnodes, n_pnodes, cell_vnodes, cell_pnodes, con_dofs, lines=None, fill=0, ordering="cm",
+             block_dofs=0):
+    """Host-only plan of GLSContext.attach_ilu on one rank (gls_ilu_plan): cell_pnodes None = pressure on the
+    velocity nodes; con_dofs the constrained DoFs (Dirichlet mask and line DoFs); lines (dofs, offsets, masters[, w])
+    as set_hanging takes them. Returns dict(perm, rowp, col, nnz, nnz_a, n_probes, probe, color, mc_solve)."""
+    L = load()
+    cv = np.ascontiguousarray(cell_vnodes, dtype=np.int32)
+    cp = None if cell_pnodes is None else np.ascontiguousarray(cell_pnodes, dtype=np.int32)
+    nc = cv.size // (k + 1) ** dim
+    con = np.ascontiguousarray(con_dofs, dtype=np.int64)
+    ld, lo, lm = (np.ascontiguousarray(a, dtype=np.int64) for a in (lines[:3] if lines is not None else ([], [0], [])))
+    n = dim * int(n_vnodes) + int(n_pnodes)
+    nnz, nnz_a, npr, mcs = C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
+    i64, vp = C.c_int64, C.c_void_p
+    L.gls_ilu_plan.argtypes = [C.c_int] * 3 + [i64] * 3 + [vp, vp, i64, vp, i64, vp, vp, vp, C.c_int, C.c_int, i64,
+                                                           vp, vp, vp, i64, vp, vp, C.POINTER(i64), C.POINTER(i64),
+                                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    args = (int(dim), int(k), int(kp), int(n_vnodes), int(n_pnodes), nc, cv.ctypes.data,
+            None if cp is None else cp.ctypes.data, len(con), con.ctypes.data, len(ld), ld.ctypes.data, lo.ctypes.data,
+            lm.ctypes.data, int(fill), {"cm": 0, "multicolor": 1}[ordering], int(block_dofs))
+    tail = (C.byref(nnz), C.byref(nnz_a), C.byref(npr), C.byref(mcs))
+    check(L.gls_ilu_plan(*args, None, None, None, 0, None, None, *tail), "gls_ilu_plan")
+    perm, probe, color = (np.zeros(n, dtype=np.int32) for _ in range(3))
+    rowp = np.zeros(n + 1, dtype=np.int32)
+    col = np.zeros(nnz.value, dtype=np.int32)
+    check(L.gls_ilu_plan(*args, perm.ctypes.data, rowp.ctypes.data, col.ctypes.data, nnz.value, probe.ctypes.data,
+                         color.ctypes.data, *tail), "gls_ilu_plan")
+    return dict(perm=perm, rowp=rowp, col=col, nnz=nnz.value, nnz_a=nnz_a.value, n_probes=npr.value, probe=probe,
+                color=color, mc_solve=bool(mcs.value))
 
 
 def cuthill_mckee(adj_off, adj, dof_off, dofs):
