@@ -1164,6 +1164,7 @@ struct Solver {
   void release() {
     release_boundary_plan();  // the plan belongs to the context destroyed below
     release_output_plan();
+    release_error_plan();
     for (gls_ctx *g : mg_levels) gls_destroy(g);
     mg_levels.clear();
     for (gls_refined_mesh *R : mg_meshes) gls_octree_mesh_destroy(R);
@@ -2409,8 +2410,7 @@ struct Solver {
     oplan = nullptr;
     oplan_refused = false;
   }
-  void write_output() {
-    SectionTimer::Scope ts(timer, "output");
+  gls_mesh_desc mesh_desc() const {  // the current mesh as the plans and the writer take it
     gls_mesh_desc D;
     std::memset(&D, 0, sizeof(D));
     D.dim = m.dim;
@@ -2430,6 +2430,11 @@ struct Solver {
     }
     D.srf = P.srf ? 1 : 0;
     for (int i = 0; i < 3; ++i) D.omega[i] = P.omega[i];
+    return D;
+  }
+  void write_output() {
+    SectionTimer::Scope ts(timer, "output");
+    const gls_mesh_desc D = mesh_desc();
     bool on_device = output_device && world == 1 && !oplan_refused;
     if (on_device && !oplan) {  // the library decides what it has a kernel for
       const int rc = gls_output_plan_create(ctx, &D, P.subdivision, &oplan);
@@ -2458,6 +2463,42 @@ struct Solver {
     ck(gls_pvd_write((P.output_path + P.output_name + ".pvd").c_str(), (int)pvd.size(), tt.data(), ff.data()),
        "gls_pvd_write");
   }
+  // The L2 error on the device (--error-eval device: gls_error_plan_create / gls_l2_error): QGauss(k+2), the
+  // analytical solution by the library's device interpreter and the two passes of l2_error() over d_present --
+  // no download of the solution. The plan follows the output plan's rules: released with the context, made at the
+  // first use after that. What the library has no kernel for (gls_error_plan_create answers GLS_EINVAL: 2D Q3, an
+  // expression nested past the interpreter's stack) and --np take the host path.
+  gls_error_plan *eplan = nullptr;
+  bool eplan_refused = false;
+  bool error_device = false;  // --error-eval
+  void release_error_plan() {
+    if (eplan) gls_error_plan_destroy(eplan);
+    eplan = nullptr;
+    eplan_refused = false;
+  }
+  bool error_on_device() {  // true: eplan is ready
+    if (!error_device || world != 1 || eplan_refused) return false;
+    if (eplan) return true;
+    const auto t0 = std::chrono::steady_clock::now();
+    const gls_mesh_desc D = mesh_desc();
+    const int rc = gls_error_plan_create(ctx, &D, P.exact.e, &eplan);  // the library decides what it has a kernel for
+    if (rc == GLS_EINVAL) {
+      if (rank == 0) std::fprintf(stderr, "L2 error: host evaluation (%s)\n", gls_last_error());
+      eplan_refused = true;
+      return false;
+    }
+    ck(rc, "gls_error_plan_create");
+    if (rank == 0) std::fprintf(stderr, "L2 error: on the device (gls_l2_error), %lld cells\n", (long long)m.nc);
+    if (timer.on) timer.add("error", 0, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    return true;
+  }
+  std::pair<double, double> l2_error_device() {
+    SectionTimer::Scope ts(timer, "error");
+    need_dev();
+    double e[2];
+    ck(gls_l2_error(ctx, eplan, d_present, time, e), "gls_l2_error");
+    return {e[0], e[1]};
+  }
   void postprocess(bool initial) {
     // output control = time: the controller decides (and records the output time: once per iteration)
     if (tc && P.output_control == GLS_OUTPUT_TIME) {
@@ -2467,7 +2508,8 @@ struct Solver {
     } else if (P.output_frequency > 0 && step % P.output_frequency == 0) {
       write_output();
     }
-    if (!initial && P.analytical) need_host();
+    const bool error_dev = !initial && P.analytical && error_on_device();
+    if (!initial && P.analytical && !error_dev) need_host();
     // post-processing lines of NavierStokesBase::postprocess (navier_stokes_base.cc:791-853)
     if (P.enstrophy && P.pp_verbose) std::printf("Enstrophy  : %s\n", g6(volume_average(true)).c_str());
     if (P.kinetic) {  // navier_stokes_base.cc:824-839
@@ -2488,7 +2530,7 @@ struct Solver {
       }
     }
     if (!initial && P.analytical) {
-      const auto e = l2_error();
+      const auto e = error_dev ? l2_error_device() : l2_error();
       if (P.method == Method::steady) errors.push_back({(double)m.nc, e.first, e.second});
       else errors.push_back({time, e.first});
       if (P.analytical_verbose && P.method != Method::steady)
@@ -3142,9 +3184,10 @@ int main(int argc, char **argv) {
   // --stats (solver iteration totals), --ilu-block-dofs N (block-Jacobi ILU subdomains of N DoFs,
   // 0 = one block), --ilu-order cm|multicolor (gls_ilu_set_options), --dump DIR (every iteration's
   // final state for the pipeline tests), --output-eval host|device (the VTU point data from the host vector or,
-  // the default, on the device from the device-resident solution).
+  // the default, on the device from the device-resident solution), --error-eval host|device (the L2 error against
+  // the analytical solution from the host vector, the default, or on the device).
   int dim = 0;
-  bool output_device = true;
+  bool output_device = true, error_device = false;
   bool mg = true, stats = false;
   int64_t ilu_block = -1;
   int ilu_order = -1;
@@ -3180,6 +3223,11 @@ int main(int argc, char **argv) {
       const char *o = argv[++i];
       if (std::strcmp(o, "host") && std::strcmp(o, "device")) die("--output-eval %s: host or device", o);
       output_device = !std::strcmp(o, "device");
+    }
+    else if (!std::strcmp(argv[i], "--error-eval") && i + 1 < argc) {
+      const char *o = argv[++i];
+      if (std::strcmp(o, "host") && std::strcmp(o, "device")) die("--error-eval %s: host or device", o);
+      error_device = !std::strcmp(o, "device");
     }
     else if (argv[i][0] != '-') file = argv[i];
     else die("unknown option %s", argv[i]);
@@ -3235,6 +3283,7 @@ int main(int argc, char **argv) {
   s.ilu_order = ilu_order;
   if (dump) s.dump_dir = dump;
   s.output_device = output_device;
+  s.error_device = error_device;
   s.run();
   if (np_ranks > 1) {
     g_comm.barrier("end");

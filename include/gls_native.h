@@ -905,6 +905,36 @@ int gls_expr_create(const char *expr, const char *vars, const char *constants, g
 int gls_expr_n_components(const gls_expr *e);
 int gls_expr_eval(const gls_expr *e, int64_t n_points, const double *values, double *out);
 void gls_expr_destroy(gls_expr *e);
+/* The same on the DEVICE: values and out are DEVICE arrays with the layouts of gls_expr_eval, the launch is queued
+ * on hip_stream (a hipStream_t; NULL: the default stream). One lane per point interprets the expression's stack
+ * bytecode with the semantics of gls_expr_eval, operation by operation: + - * unary minus, comparisons, && || !,
+ * ?:, abs floor ceil rint int sign, min max sum, constants and variables give the host's bits; / sqrt ^ pow and the
+ * transcendental functions are the device math library's (within a few ulp of the host's). The operand stack
+ * lives in LDS and holds 16 entries: a more deeply nested expression is GLS_EINVAL with a message, before any
+ * launch. The device copy of the program is made at the first call (not thread-safe for one expression) and
+ * released by gls_expr_destroy. Two calls on the same input are bitwise equal. */
+int gls_expr_eval_device(const gls_expr *e, int64_t n_points, const double *values, double *out, void *hip_stream);
+
+/* The L2 error of a DEVICE solution vector against an analytical solution on the device (the reference's
+ * calculate_L2_error, navier_stokes_base.cc:887): QGauss(k+2) on every cell of the context, the exact solution
+ * `exact` (variables: the dim coordinates, then t; components: the dim velocity components and optionally the
+ * pressure -- without it the exact pressure is 0) evaluated by the device interpreter at the mapped points and at
+ * `time`. Pass 1 sums int p_h, int p and the volume (box meshes: sum of JxW; mapped meshes: the sum of the Q1 cell
+ * measures, GridTools::volume), pass 2 takes the two means from it:
+ *   out[0] = sqrt(int |u_h - u|^2), out[1] = sqrt(int ((p_h - mean p_h) - (p - mean p))^2)   (HOST, one download).
+ * gls_error_plan_create uploads the geometry the Gauss points need (box cells: cell_x0 / cell_h; mapped cells:
+ * cell_support) and the 1D tables at the Gauss abscissae; mesh must be the description the context was created
+ * from (dim, k, kp, n_cells and map_degree are checked); rebuild the plan after an adaptation. `exact` must
+ * outlive the plan. Every layout of a context: brick, per-cell box, mapped, with hanging lines (the vector holds
+ * the constrained values). The work is queued on the context's stream; per-block partials, then one ordered stage:
+ * no atomics, two calls on the same input are bitwise equal. Kernels exist for dim 2, 3 and (k, kp) in {(1,1),
+ * (2,1), (2,2)}, box and mapped (map_degree <= 3); anything else (2D Q3), an expression whose stack is deeper than
+ * the interpreter's, a wrong variable count, fewer than dim components or a distributed context is GLS_EINVAL at
+ * gls_error_plan_create. */
+typedef struct gls_error_plan gls_error_plan;
+int gls_error_plan_create(gls_ctx *ctx, const gls_mesh_desc *mesh, const gls_expr *exact, gls_error_plan **plan);
+int gls_error_plan_destroy(gls_error_plan *plan);
+int gls_l2_error(gls_ctx *ctx, gls_error_plan *plan, const double *sol, double time, double out[2]);
 
 /* Output: NavierStokesBase::write_output_results (navier_stokes_base.cc:998-1086) — one patch per
  * cell with `subdivision` intervals (Lagrange cells when k > 1), point data velocity, pressure,

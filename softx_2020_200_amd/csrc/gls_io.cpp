@@ -29,6 +29,7 @@
 
 #include "../../include/gls_native.h"
 #include "gls_error.hpp"
+#include "gls_expr_program.hpp"
 
 namespace {
 
@@ -175,9 +176,7 @@ void gls_prm_destroy(gls_prm *p) { delete p; }
 // ============================================================================================
 namespace {
 
-enum Op : int {
-  PUSH_C, PUSH_V, NEG, ADD, SUB, MUL, DIV, POW, LT, GT, LE, GE, EQ, NE, AND, OR, NOT, SEL, F1, F2, FMIN, FMAX, FSUM
-};
+using namespace gls::expr;  // the opcodes and function indices (gls_expr_program.hpp)
 typedef double (*Fn1)(double);
 typedef double (*Fn2)(double, double);
 
@@ -200,6 +199,9 @@ const Fun1 kFun1[] = {
 };
 struct Fun2 { const char *name; Fn2 f; };
 const Fun2 kFun2[] = {{"atan2", std::atan2}, {"pow", std::pow}, {"fmod", std::fmod}};
+// the device interpreter dispatches on these indices
+static_assert(sizeof(kFun1) / sizeof(kFun1[0]) == F1_COUNT && sizeof(kFun2) / sizeof(kFun2[0]) == F2_COUNT,
+              "kFun1 / kFun2 and the indices of gls_expr_program.hpp");
 
 struct Instr {
   int op;
@@ -526,7 +528,24 @@ struct gls_expr {
   std::vector<std::string> vars;
   std::vector<Compiled> comps;
   int max_stack = 1;
+  mutable void *device = nullptr;  // the program on the device, made by the first gls_expr_eval_device
+  ~gls_expr() {
+    if (device) gls::expr::device_release(device);
+  }
 };
+
+void gls_io_expr_flatten(const gls_expr *e, gls::expr::FlatProgram &out) {
+  out = gls::expr::FlatProgram();
+  out.n_vars = (int)e->vars.size();
+  out.n_comps = (int)e->comps.size();
+  out.off.push_back(0);
+  for (const Compiled &c : e->comps) {
+    for (const Instr &in : c.code) out.code.push_back({(int32_t)in.op, (int32_t)in.i, in.c});
+    out.off.push_back((int32_t)out.code.size());
+    out.max_stack = std::max(out.max_stack, c.max_stack);
+  }
+}
+void **gls_io_expr_device_slot(const gls_expr *e) { return &e->device; }
 
 extern "C" {
 

@@ -240,6 +240,24 @@ hipError_t launch_output_fields(int dim, int k, int kp, int map_degree, int subd
                                 double *pts, double *vel, double *pre, double *vort, double *qcr, double *eul,
                                 hipStream_t s);
 
+// ---- L2 error against an analytical solution (gls_error.hip): QGauss(k+2), one lane per quadrature point, the
+// exact solution from the expression's program (gls_expr_device.hpp: variables x, y [, z], t; components u, v [, w]
+// [, p]) at the mapped points and `time`. Two passes queued on s: out[0..2] = int p_h, int p, volume (volume >= 0
+// replaces the sum of JxW), then out[3] = int |u_h - u|^2 and out[4] = int ((p_h - mean p_h) - (p - mean p))^2;
+// out: 6 doubles, partial: l2_error_blocks(...) * 3 doubles, folded in a fixed order (bitwise reproducible).
+// x0h / support as for the output fields; tab = Vv [k+2][k+1] | Vp [k+2][kp+1] | xq [k+2] | wq [k+2] | Vm
+// [k+2][map_degree+1] | Dm (the last two for mapped cells only) at the Gauss abscissae. Instantiated for dim 2, 3
+// and (k, kp) in {(1,1), (2,1), (2,2)}, box and mapped (map_degree <= 3); max_stack <= 16.
+namespace expr {
+struct DeviceProgram;
+}
+bool l2_error_supported(int dim, int k, int kp, int map_degree, int max_stack);
+int64_t l2_error_blocks(int dim, int k, int kp, int map_degree, int max_stack, int64_t n_cells);
+hipError_t launch_l2_error(int dim, int k, int kp, int map_degree, const int32_t *cell_vnodes, const int32_t *cell_pnodes,
+                           const double *sol, int64_t pbase, const double *x0h, const double *support, const double *tab,
+                           int64_t n_cells, const expr::DeviceProgram &exact, double time, double volume, double *partial,
+                           double *out, hipStream_t s);
+
 // ---- geometric multigrid (gls_mg_kernels.hip): nested Qk node lattices (boxes), k <= 2
 hipError_t mg_inject(const double *fine, double *coarse, const int nf[3], const int nc[3], hipStream_t s);
 // one-pass 3D transfer with per-axis tap tables [n_out][5] (index, weight) and tap counts [n_out]

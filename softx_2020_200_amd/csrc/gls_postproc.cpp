@@ -1,5 +1,6 @@
 // gls_postproc.cpp -- post-processing entry points of the C-ABI: the Kelly error indicator, boundary forces and
-// torques, the flow diagnostics (CFL, kinetic energy, enstrophy) and the VTU point data evaluated on the device.
+// torques, the flow diagnostics (CFL, kinetic energy, enstrophy), the VTU point data evaluated on the device and
+// the L2 error against an analytical solution.
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "gls_ctx.hpp"
+#include "gls_expr_device.hpp"
 
 using namespace gls_impl;
 
@@ -471,6 +473,116 @@ int gls_vtu_write_device(gls_ctx *c, gls_output_plan *p, const double *sol, cons
                  wr - enc);
   }
   return rc;
+}
+
+// --------------------------------------------------------------------------------------------
+// L2 error against an analytical solution (the application's l2_error(), the reference's calculate_L2_error):
+// the geometry of one mesh and the 1D tables at the QGauss(k+2) abscissae uploaded once (plan), every evaluation
+// two passes over all cells on the device and one download of the sums
+// --------------------------------------------------------------------------------------------
+struct gls_error_plan {
+  gls_ctx *ctx = nullptr;
+  gls::expr::DeviceProgram exact;
+  int64_t n_cells = 0;
+  double volume = -1.0;  // general meshes: the sum of the Q1 cell measures; boxes: < 0, the sum of JxW
+  DevBuf<double> x0h, support, tab, partial, out;
+};
+
+int gls_error_plan_create(gls_ctx *c, const gls_mesh_desc *m, const gls_expr *exact, gls_error_plan **out) {
+  GLS_TRY(check_ctx(c));
+  if (!m || !exact || !out) return set_err(GLS_EINVAL, "gls_error_plan_create: null argument");
+  if (c->dist.on) return set_err(GLS_EINVAL, "gls_error_plan_create: a distributed context is not served");
+  if (m->dim != c->dim || m->k != c->k || m->kp != c->kp || m->n_cells != c->n_cells || m->map_degree != c->map_degree)
+    return set_err(GLS_EINVAL,
+                   "gls_error_plan_create: the mesh (%dD FE_Q(%d)-FE_Q(%d), %d cells, mapping degree %d) is not the "
+                   "context's (%dD FE_Q(%d)-FE_Q(%d), %d cells, mapping degree %d)",
+                   m->dim, m->k, m->kp, m->n_cells, m->map_degree, c->dim, c->k, c->kp, c->n_cells, c->map_degree);
+  const int dim = c->dim, md = c->map_degree, k1 = c->k + 1, kp1 = c->kp + 1, nq1 = c->k + 2, nm = md ? md + 1 : 0;
+  if (!gls::l2_error_supported(dim, c->k, c->kp, md, 1))
+    return set_err(GLS_EINVAL,
+                   "gls_error_plan_create: FE_Q(%d)-FE_Q(%d) in %dD with mapping degree %d has no L2 error kernel "
+                   "(velocity / pressure orders (1,1), (2,1), (2,2), 2D Q3 is not supported; mapping degree <= 3)",
+                   c->k, c->kp, dim, md);
+  std::unique_ptr<gls_error_plan> p(new gls_error_plan);
+  GLS_TRY(gls::expr::device_program(exact, "gls_error_plan_create", &p->exact));  // GLS_EINVAL: stack past the cap
+  if (p->exact.n_vars != dim + 1)
+    return set_err(GLS_EINVAL, "gls_error_plan_create: the analytical solution has %d variables, expected %d (%s, t)",
+                   p->exact.n_vars, dim + 1, dim == 3 ? "x, y, z" : "x, y");
+  if (p->exact.n_comps < dim)
+    return set_err(GLS_EINVAL,
+                   "gls_error_plan_create: the analytical solution has %d components, expected the %d velocity "
+                   "components and optionally the pressure",
+                   p->exact.n_comps, dim);
+  if (!gls::l2_error_supported(dim, c->k, c->kp, md, p->exact.max_stack))
+    return set_err(GLS_EINVAL, "gls_error_plan_create: no launch shape for an operand stack of %d entries",
+                   p->exact.max_stack);
+  if (md ? !m->cell_support : !m->cell_h)
+    return set_err(GLS_EINVAL, "gls_error_plan_create: the mesh has no %s", md ? "cell_support" : "cell_h");
+  if (!c->cell_pnodes.p && c->kp != c->k) return set_err(GLS_EINVAL, "gls_error_plan_create: the context has no cell_pnodes");
+  p->ctx = c;
+  const size_t nc = (size_t)c->n_cells;
+  p->n_cells = c->n_cells;
+  if (md) {
+    const size_t nsup = (size_t)gls::ipow(md + 1, dim);
+    GLS_TRY(p->support.upload(m->cell_support, nc * nsup * dim));
+    p->volume = 0.0;  // GridTools::volume: the cells' Q1 measures, summed in cell order
+    for (size_t cix = 0; cix < nc; ++cix) p->volume += corner_measure(dim, md, m->cell_support + cix * nsup * dim);
+  } else {
+    std::vector<double> x0h(nc * 2 * dim);
+    for (size_t cix = 0; cix < nc; ++cix)
+      for (int d = 0; d < dim; ++d) {
+        x0h[cix * 2 * dim + d] = m->cell_x0 ? m->cell_x0[cix * dim + d] : 0.0;
+        x0h[cix * 2 * dim + dim + d] = m->cell_h[cix * dim + d];
+      }
+    GLS_TRY(p->x0h.upload(x0h.data(), x0h.size()));
+  }
+  // Vv | Vp | xq | wq | Vm | Dm at the QGauss(k+2) abscissae
+  std::vector<double> tab((size_t)nq1 * (k1 + kp1 + 2 + 2 * nm)), xq((size_t)nq1), wq((size_t)nq1);
+  gauss_points(nq1, xq.data(), wq.data());
+  double *tVv = tab.data(), *tVp = tVv + nq1 * k1, *tX = tVp + nq1 * kp1, *tW = tX + nq1, *tVm = tW + nq1,
+         *tDm = tVm + nq1 * nm;
+  double xn[gls::kMaxNodes1D], dv, ddv;
+  for (int q = 0; q < nq1; ++q) {
+    tX[q] = xq[(size_t)q];
+    tW[q] = wq[(size_t)q];
+    lobatto_points(c->k, xn);
+    for (int a = 0; a < k1; ++a) lagrange_1d(c->k, xn, a, xq[(size_t)q], tVv[q * k1 + a], dv, ddv);
+    lobatto_points(c->kp, xn);
+    for (int a = 0; a < kp1; ++a) lagrange_1d(c->kp, xn, a, xq[(size_t)q], tVp[q * kp1 + a], dv, ddv);
+    if (md) {
+      lobatto_points(md, xn);
+      for (int a = 0; a < nm; ++a) lagrange_1d(md, xn, a, xq[(size_t)q], tVm[q * nm + a], tDm[q * nm + a], ddv);
+    }
+  }
+  GLS_TRY(p->tab.upload(tab.data(), tab.size()));
+  GLS_TRY(p->partial.alloc((size_t)gls::l2_error_blocks(dim, c->k, c->kp, md, p->exact.max_stack, c->n_cells) * 3));
+  GLS_TRY(p->out.alloc(6));
+  *out = p.release();
+  return GLS_OK;
+}
+
+int gls_error_plan_destroy(gls_error_plan *plan) {
+  delete plan;
+  return GLS_OK;
+}
+
+int gls_l2_error(gls_ctx *c, gls_error_plan *p, const double *sol, double time, double out[2]) {
+  GLS_TRY(check_ctx(c));
+  if (!p || p->ctx != c) return set_err(GLS_EINVAL, "gls_l2_error: the plan belongs to another context");
+  if (!sol || !out) return set_err(GLS_EINVAL, "gls_l2_error: bad arguments");
+  if (p->n_cells != c->n_cells) return set_err(GLS_EINVAL, "gls_l2_error: the context has changed since the plan was made");
+  out[0] = out[1] = 0.0;
+  if (c->n_cells == 0) return GLS_OK;
+  const int32_t *pn = c->cell_pnodes.p ? c->cell_pnodes.p : c->cell_vnodes.p;  // equal order: shared nodes
+  HIP_TRY(gls::launch_l2_error(c->dim, c->k, c->kp, c->map_degree, c->cell_vnodes.p, pn, sol,
+                               (int64_t)c->dim * c->n_vnodes, p->x0h.p, p->support.p, p->tab.p, c->n_cells, p->exact, time,
+                               p->volume, p->partial.p, p->out.p, c->stream));
+  double h[6];
+  HIP_TRY(hipMemcpyAsync(h, p->out.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  out[0] = std::sqrt(h[3]);
+  out[1] = std::sqrt(h[4]);
+  return GLS_OK;
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@ def _bind():
     L.gls_expr_eval.argtypes = [vp, i64, d, d]
     L.gls_expr_destroy.argtypes = [vp]
     L.gls_expr_destroy.restype = None
+    L.gls_expr_eval_device.argtypes = [vp, i64, vp, vp, vp]
     L.gls_vtu_write.argtypes = [cp, C.POINTER(MeshDesc), d, C.c_int, C.c_int, C.c_int]
     L.gls_pvtu_write.argtypes = [cp, C.c_int, C.c_int, C.c_int, C.POINTER(cp)]
     L.gls_pvd_write.argtypes = [cp, C.c_int, d, C.POINTER(cp)]
@@ -91,6 +92,20 @@ class Expr:
         out = np.zeros((v.shape[0], self.n_components))
         check(self.L.gls_expr_eval(self.h, v.shape[0], v.ctypes.data_as(C.POINTER(C.c_double)),
                                    out.ctypes.data_as(C.POINTER(C.c_double))), "gls_expr_eval")
+        return out
+
+    def eval_device(self, values, out=None, stream=None):
+        """values: a float64 device tensor [n_points, n_vars] -> a device tensor [n_points, n_components], evaluated
+        by the device interpreter (gls_expr_eval_device) on `stream` (a raw hipStream_t; None: the default stream)"""
+        import torch
+        v = values.contiguous().reshape(-1, self.n_vars) if self.n_vars else values
+        if v.dtype != torch.float64 or not v.is_cuda:
+            raise GLSError("eval_device: values must be a float64 device tensor")
+        n = v.shape[0]
+        if out is None:
+            out = torch.empty((n, self.n_components), dtype=torch.float64, device=v.device)
+        check(self.L.gls_expr_eval_device(self.h, n, v.data_ptr() or None, out.data_ptr() or None, stream),
+              "gls_expr_eval_device")
         return out
 
 

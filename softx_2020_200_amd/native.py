@@ -34,7 +34,8 @@ EXPORTS = [
     "gls_mg_attach", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_ilu_plan", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
     "gls_mg_residual_restrict", "gls_mg_prolong_smooth",
     "gls_prm_parse", "gls_prm_get", "gls_prm_n_entries", "gls_prm_entry", "gls_prm_destroy",
-    "gls_expr_create", "gls_expr_n_components", "gls_expr_eval", "gls_expr_destroy",
+    "gls_expr_create", "gls_expr_n_components", "gls_expr_eval", "gls_expr_destroy", "gls_expr_eval_device",
+    "gls_error_plan_create", "gls_error_plan_destroy", "gls_l2_error",
     "gls_vtu_write", "gls_pvtu_write", "gls_pvd_write",
     "gls_set_hanging", "gls_mesh_refined_create", "gls_mesh_refined_destroy", "gls_octree_create", "gls_octree_destroy", "gls_octree_info",
     "gls_octree_cells", "gls_octree_adapt", "gls_octree_prepare", "gls_octree_mesh", "gls_octree_mesh_destroy", "gls_octree_transfer", "gls_octree_faces", "gls_kelly_estimate_faces",
@@ -238,6 +239,9 @@ def load():
     L.gls_output_plan_destroy.argtypes = [vp]
     L.gls_output_fields.argtypes = [vp, vp, vp, d, d, d, d, d, d]
     L.gls_vtu_write_device.argtypes = [vp, vp, vp, C.c_char_p, C.c_int, C.c_int]
+    L.gls_error_plan_create.argtypes = [vp, C.POINTER(MeshDesc), vp, C.POINTER(vp)]
+    L.gls_error_plan_destroy.argtypes = [vp]
+    L.gls_l2_error.argtypes = [vp, vp, vp, C.c_double, d]
     L.gls_time_control_create.argtypes = [C.POINTER(TimeControlParams), C.POINTER(vp)]
     L.gls_time_control_destroy.argtypes = [vp]
     L.gls_time_control_destroy.restype = None
@@ -1010,6 +1014,13 @@ class GLSContext:
         after an adaptation."""
         return OutputPlan(self, mesh, subdivision, srf, omega)
 
+    def error_plan(self, mesh, expr):
+        """The L2 error of a device solution vector against an analytical solution on this context's cells
+        (gls_error_plan_create): mesh is the mesh the context was created from, expr an io.Expr over the
+        variables x, y [, z], t with the dim velocity components and optionally the pressure. Make a new plan
+        after an adaptation."""
+        return ErrorPlan(self, mesh, expr)
+
     def mg_transfer(self, level, direction, v, out):
         """Restrict (direction 0: level -> level+1) or prolongate (1: level+1 -> level) a device vector."""
         check(self.L.gls_mg_transfer(self.h, int(level), int(direction), _ptr(v), _ptr(out)), "gls_mg_transfer")
@@ -1148,6 +1159,35 @@ class OutputPlan:
         """one VTU piece of a device solution vector: the fields on the device, gls_vtu_write's file writer"""
         check(self.L.gls_vtu_write_device(self.ctx.h, self.h, _ptr(sol), str(filename).encode(), int(subdomain),
                                           1 if binary else 0), "gls_vtu_write_device")
+
+
+class ErrorPlan:
+    """One gls_error_plan: the Gauss-point geometry and tables of one mesh on the device and the exact solution."""
+
+    def __init__(self, ctx, mesh, expr):
+        self.ctx, self.L, self.expr = ctx, ctx.L, expr  # the expression must outlive the plan
+        D, keep = mesh_desc(mesh)
+        h = C.c_void_p()
+        check(self.L.gls_error_plan_create(ctx.h, C.byref(D), expr.h, C.byref(h)), "gls_error_plan_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gls_error_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def l2_error(self, sol, time=0.0):
+        """(|u_h - u|_L2, L2 norm of the mean-free pressure difference) of a device solution vector at `time`
+        (gls_l2_error)"""
+        out = np.zeros(2)
+        check(self.L.gls_l2_error(self.ctx.h, self.h, _ptr(sol), float(time), _dp(out)), "gls_l2_error")
+        return float(out[0]), float(out[1])
 
 
 class UMesh:
