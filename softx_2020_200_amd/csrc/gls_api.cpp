@@ -1,8 +1,8 @@
-// gls_api.cpp — C-ABI implementation: context lifecycle, operator dispatch, multigrid, GMRES / BiCGStab, Newton,
+// gls_api.cpp — C-ABI implementation: context lifecycle, operator dispatch, GMRES / BiCGStab, Newton,
 // hyper_cube mesh and time-integration coefficients; the last-error string. Host C++17 over HIP. The context struct
-// and the helpers shared with the other host files: gls_ctx.hpp; the assembled ILU: gls_ilu.cpp (its host-only
-// plan: gls_ilu_plan.cpp); Kelly, boundary loads, flow diagnostics and device output: gls_postproc.cpp; the RCCL
-// transport: gls_rccl.cpp.
+// and the helpers shared with the other host files: gls_ctx.hpp; the multigrid: gls_mg.cpp (its coarsest-level
+// direct solve: gls_mg_coarse.cpp); the assembled ILU: gls_ilu.cpp (its host-only plan: gls_ilu_plan.cpp); Kelly,
+// boundary loads, flow diagnostics and device output: gls_postproc.cpp; the RCCL transport: gls_rccl.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,7 +19,6 @@
 #include <string>
 #include <vector>
 #include <set>
-#include <thread>
 
 #include "gls_ctx.hpp"
 
@@ -393,14 +392,6 @@ void set_colors(gls_ctx *c, gls::OpParams &P, double *acc) {
   P.slabf = nullptr;
 }
 
-// brick launch output: slab (allocated on first use) or nullptr (atomics into a zeroed y)
-double *brick_slab(gls_ctx *c) {
-  if (!c->use_slab) return nullptr;
-  const size_t n = (size_t)(c->n_cells / 8) * gls::brick_boundary_nodes(c->k) * 4;
-  if (c->slab.n != n && c->slab.alloc(n) != GLS_OK) return nullptr;
-  return c->slab.p;
-}
-
 // MappingQ(md) on one cell at the QGauss(nq1d) points: x_q, JxW, J^-1, G = J^-1 J^-T and the
 // Hessian correction c_k = sum_ab G_ab d2x_k/dxi_a dxi_b (kGeo layout, gls_common.hpp); support
 // points S[(md+1)^dim][dim] on the equidistant lattice (Gauss-Lobatto for md <= 2)
@@ -489,6 +480,14 @@ void mapped_geometry(int dim, int md, int nq1d, const double *S, double *out) {
 
 }  // namespace
 namespace gls_impl {  // declared in gls_ctx.hpp
+// brick launch output: slab (allocated on first use) or nullptr (atomics into a zeroed y)
+double *brick_slab(gls_ctx *c) {
+  if (!c->use_slab) return nullptr;
+  const size_t n = (size_t)(c->n_cells / 8) * gls::brick_boundary_nodes(c->k) * 4;
+  if (c->slab.n != n && c->slab.alloc(n) != GLS_OK) return nullptr;
+  return c->slab.p;
+}
+
 // cell->measure() of a mapped cell from its corner support points (exact bilinear / trilinear
 // volume: 2-point Gauss of the multilinear det J)
 double corner_measure(int dim, int md, const double *S) {
@@ -556,9 +555,6 @@ gls::OpParams make_params(gls_ctx *c, bool jac) {
   }
   return P;
 }
-}  // namespace gls_impl
-namespace {
-
 // ---- distributed hooks (no-ops on a single rank)
 int dist_import(gls_ctx *c, double *x) {
   if (!c->dist.on) return GLS_OK;
@@ -574,6 +570,43 @@ int dist_import(gls_ctx *c, double *x) {
   HIP_TRY(gls::vec_unpack_nodes(x, c->dist.recv_nodes.p, c->dist.n_recv, voff, c->dist.recv_buf, 0, c->stream));
   return GLS_OK;
 }
+int dist_export_add(gls_ctx *c, double *y) {
+  if (!c->dist.on) return GLS_OK;
+  if (c->dist.dofs) {
+    HIP_TRY(gls::vec_pack_dofs(y, c->dist.recv_nodes.p, c->dist.n_recv, c->dist.recv_buf, c->stream));
+    if (c->dist.xchg(c->dist.user, 1) != 0) return set_err(GLS_ECOMM, "ghost export exchange failed");
+    HIP_TRY(gls::vec_add_dofs_ordered(y, c->dist.add_u.p, c->dist.add_off.p, c->dist.add_slot.p, (int64_t)c->dist.add_u.n,
+                                      c->dist.send_buf, c->stream));
+    return GLS_OK;
+  }
+  const int64_t voff = 3 * (int64_t)c->n_vnodes;
+  HIP_TRY(gls::vec_pack_nodes(y, c->dist.recv_nodes.p, c->dist.n_recv, voff, c->dist.recv_buf, c->stream));
+  if (c->dist.xchg(c->dist.user, 1) != 0) return set_err(GLS_ECOMM, "ghost export exchange failed");
+  HIP_TRY(gls::vec_add_nodes_ordered(y, c->dist.add_u.p, c->dist.add_off.p, c->dist.add_slot.p, (int64_t)c->dist.add_u.n,
+                                     voff, c->dist.send_buf, c->stream));
+  return GLS_OK;
+}
+// in-place sum over ranks of a device vector through c's transport (RCCL: one call; callback transports
+// through their reduction buffer in chunks of GLS_RED_BUF_MIN values)
+int dist_allreduce_vector(gls_ctx *c, double *v, int64_t n) {
+  auto &D = c->dist;
+  if (!D.on) return GLS_OK;
+  if (D.comm) {
+    if (D.allreduce(D.user, v, (int)n) != 0) return set_err(GLS_ECOMM, "vector all-reduce failed");
+    return GLS_OK;
+  }
+  hipStream_t s = c->stream;
+  for (int64_t o = 0; o < n; o += GLS_RED_BUF_MIN) {
+    const int len = (int)std::min<int64_t>(GLS_RED_BUF_MIN, n - o);
+    HIP_TRY(hipMemcpyAsync(D.red_buf, v + o, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
+    if (D.allreduce(D.user, D.red_buf, len) != 0) return set_err(GLS_ECOMM, "vector all-reduce failed");
+    HIP_TRY(hipMemcpyAsync(v + o, D.red_buf, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
+  }
+  return GLS_OK;
+}
+}  // namespace gls_impl
+namespace {
+
 // export-add order: every owned entry's incoming exchange slots in ascending slot (= neighbour) order,
 // so the sums over several neighbours are deterministic
 int upload_export_order(gls_ctx::Dist &D, const int32_t *send, int64_t ns) {
@@ -595,22 +628,6 @@ int upload_export_order(gls_ctx::Dist &D, const int32_t *send, int64_t ns) {
   GLS_TRY(D.add_u.upload(au.data(), au.size()));
   GLS_TRY(D.add_off.upload(aoff.data(), au.empty() ? 0 : aoff.size()));
   return D.add_slot.upload(aslot.data(), aslot.size());
-}
-int dist_export_add(gls_ctx *c, double *y) {
-  if (!c->dist.on) return GLS_OK;
-  if (c->dist.dofs) {
-    HIP_TRY(gls::vec_pack_dofs(y, c->dist.recv_nodes.p, c->dist.n_recv, c->dist.recv_buf, c->stream));
-    if (c->dist.xchg(c->dist.user, 1) != 0) return set_err(GLS_ECOMM, "ghost export exchange failed");
-    HIP_TRY(gls::vec_add_dofs_ordered(y, c->dist.add_u.p, c->dist.add_off.p, c->dist.add_slot.p, (int64_t)c->dist.add_u.n,
-                                      c->dist.send_buf, c->stream));
-    return GLS_OK;
-  }
-  const int64_t voff = 3 * (int64_t)c->n_vnodes;
-  HIP_TRY(gls::vec_pack_nodes(y, c->dist.recv_nodes.p, c->dist.n_recv, voff, c->dist.recv_buf, c->stream));
-  if (c->dist.xchg(c->dist.user, 1) != 0) return set_err(GLS_ECOMM, "ghost export exchange failed");
-  HIP_TRY(gls::vec_add_nodes_ordered(y, c->dist.add_u.p, c->dist.add_off.p, c->dist.add_slot.p, (int64_t)c->dist.add_u.n,
-                                     voff, c->dist.send_buf, c->stream));
-  return GLS_OK;
 }
 // out[k] = sum over OWNED DoFs of A[k] . w, reduced over ranks (host result)
 int dist_multidot(gls_ctx *c, const double *A, int64_t lda, int nk, const double *w, double *host_out) {
@@ -637,24 +654,6 @@ int lin_f32_target(gls_ctx *c, gls::OpParams &P) {
   if (c->qdata32.n != c->qdata.n) GLS_TRY(c->qdata32.alloc(c->qdata.n));
   P.qdf = c->qdata32.p;
   P.oseen = c->smooth_oseen ? 1 : 0;  // the Oseen smoother reads u and tau only: the other FP32 rows are not written
-  return GLS_OK;
-}
-
-// J.v linearization (u, grad u, tau, R_s at every quadrature point), once per state
-int ensure_qdata(gls_ctx *c) {
-  if (c->qd_valid) return GLS_OK;
-  const size_t n = gls::brick_qdata_size(c->k, c->n_cells);
-  if (c->qdata.n != n) GLS_TRY(c->qdata.alloc(n));
-  gls::OpParams P = make_params(c, true);
-  P.qd = c->qdata.p;
-  GLS_TRY(lin_f32_target(c, P));
-  {
-    TimedLaunch t(c, 3);
-    HIP_TRY(gls::launch_brick_kernel(c->k, gls::MODE_LIN, P, c->tables, c->stream));
-  }
-  c->qd_valid = true;
-  c->qd32_valid = P.qdf != nullptr;
-  c->qd32_partial = P.qdf != nullptr && P.oseen;
   return GLS_OK;
 }
 
@@ -722,6 +721,24 @@ bool split_jv_enabled(gls_ctx *c) {
 
 }  // namespace
 namespace gls_impl {  // declared in gls_ctx.hpp
+// J.v linearization (u, grad u, tau, R_s at every quadrature point), once per state
+int ensure_qdata(gls_ctx *c) {
+  if (c->qd_valid) return GLS_OK;
+  const size_t n = gls::brick_qdata_size(c->k, c->n_cells);
+  if (c->qdata.n != n) GLS_TRY(c->qdata.alloc(n));
+  gls::OpParams P = make_params(c, true);
+  P.qd = c->qdata.p;
+  GLS_TRY(lin_f32_target(c, P));
+  {
+    TimedLaunch t(c, 3);
+    HIP_TRY(gls::launch_brick_kernel(c->k, gls::MODE_LIN, P, c->tables, c->stream));
+  }
+  c->qd_valid = true;
+  c->qd32_valid = P.qdf != nullptr;
+  c->qd32_partial = P.qdf != nullptr && P.oseen;
+  return GLS_OK;
+}
+
 // slots of every node in the per-cell element vectors [n_cells][NV*dim + NP], ascending (cell, local
 // node) order: the fixed summation order of gather_element_vectors
 int ensure_element_maps(gls_ctx *c) {
@@ -1463,12 +1480,13 @@ int gls_jacobian_apply(gls_ctx *c, const double *v, double *y) {
   return GLS_OK;
 }
 
-namespace {
+}  // extern "C"
+namespace gls_impl {  // declared in gls_ctx.hpp
 // the V-cycle's operator on level g: J.v in FP32 arithmetic from the FP32 linearization when the
 // level smooths in mixed precision (brick path), else the FP64 gls_jacobian_apply. Same
 // constraint handling (constrained rows D_c v) and ghost exchange as gls_jacobian_apply.
 // full = false: u and tau suffice (the Oseen smoother operator); else every row of the FP32 copy
-int ensure_qdata32(gls_ctx *g, bool full = true) {
+int ensure_qdata32(gls_ctx *g, bool full) {
   GLS_TRY(ensure_qdata(g));
   if (!g->qd32_valid || (full && g->qd32_partial)) {
     if (g->qdata32.n != g->qdata.n) GLS_TRY(g->qdata32.alloc(g->qdata.n));
@@ -1494,8 +1512,7 @@ bool first_sweep_fusable(gls_ctx *g) {
          !g->hang.on && g->k == 2 && g->cube_nb1 > 0 && g->use_slab && gls::pencil_enabled() &&
          std::getenv("GLS_MG_NO_FUSE") == nullptr;
 }
-int jacobian_apply_f32(gls_ctx *g, const double *v, double *y, const double *rb = nullptr, double first_omega = 0.0,
-                       bool oseen = false) {
+int jacobian_apply_f32(gls_ctx *g, const double *v, double *y, const double *rb, double first_omega, bool oseen) {
   if (!g->u) return set_err(GLS_EINVAL, "gls_set_state was not called");
   GLS_TRY(ensure_diag(g));
   GLS_TRY(ensure_qdata32(g, !oseen));
@@ -1534,7 +1551,7 @@ int jacobian_apply_f32(gls_ctx *g, const double *v, double *y, const double *rb 
   return GLS_OK;
 }
 // y = A v with the level's smoothing operator; rb != nullptr: y = rb - A v
-int smoother_apply(gls_ctx *g, const double *v, double *y, const double *rb = nullptr) {
+int smoother_apply(gls_ctx *g, const double *v, double *y, const double *rb) {
   if (g->smooth_f32 && g->use_brick && g->use_qdata) return jacobian_apply_f32(g, v, y, rb, 0.0, g->smooth_oseen);
   g->oct.f32_next = g->smooth_f32 && g->oct.on;  // adapted forest: its bricks in FP32, the other cells FP64
   const int rc = gls_jacobian_apply(g, v, y);
@@ -1543,14 +1560,8 @@ int smoother_apply(gls_ctx *g, const double *v, double *y, const double *rb = nu
   if (rb) HIP_TRY(gls::vec_axpby(y, 1.0, rb, -1.0, g->n_dofs, g->stream));
   return GLS_OK;
 }
-// one damped-Jacobi sweep x <- x + omega D^-1 (b - A x) with the smoother's operator A (constrained
-// rows D_c x). Single rank on the brick path: fused into the J.v (brick-interior nodes) and the slab
-// sum (brick-surface nodes), so A x is never stored; otherwise smoother_apply + mg_jacobi_update.
-// pxc != nullptr (only where mg_fused_prolong_ok): the sweep starts from x + P pxc, the coarse correction of the
-// next-coarser nested level interpolated in the J.v's gather; y (scratch) carries x + P pxc of the brick-surface
-// nodes from the J.v to the slab sum.
 // one ILU(0) smoothing sweep x <- x + M^-1 (b - A x) (M = the level's ILU(0), undamped; z: scratch)
-int ilu_sweep(gls_ctx *g, double *x, const double *b, double *y, double *z) {
+static int ilu_sweep(gls_ctx *g, double *x, const double *b, double *y, double *z) {
   GLS_TRY(ensure_ilu(g));
   GLS_TRY(gls_jacobian_apply(g, x, y));
   HIP_TRY(gls::vec_axpby(y, 1.0, b, -1.0, g->n_dofs, g->stream));  // y = b - A x
@@ -1558,8 +1569,13 @@ int ilu_sweep(gls_ctx *g, double *x, const double *b, double *y, double *z) {
   HIP_TRY(gls::vec_axpy(x, 1.0, z, g->n_dofs, g->stream));
   return GLS_OK;
 }
-int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double omega, double *z = nullptr,
-                   const double *pxc = nullptr) {
+// one damped-Jacobi sweep x <- x + omega D^-1 (b - A x) with the smoother's operator A (constrained
+// rows D_c x). Single rank on the brick path: fused into the J.v (brick-interior nodes) and the slab
+// sum (brick-surface nodes), so A x is never stored; otherwise smoother_apply + mg_jacobi_update.
+// pxc != nullptr (only where mg_fused_prolong_ok): the sweep starts from x + P pxc, the coarse correction of the
+// next-coarser nested level interpolated in the J.v's gather; y (scratch) carries x + P pxc of the brick-surface
+// nodes from the J.v to the slab sum.
+int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double omega, double *z, const double *pxc) {
   const bool nofuse = std::getenv("GLS_MG_NO_FUSE") != nullptr;
   const bool brick = g->use_brick && g->use_qdata && (g->use_colors || brick_slab(g)) && !g->dist.on &&
                      !g->hang.on && gls::brick_fused_jacobi_supported(g->k);
@@ -1608,7 +1624,8 @@ int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double ome
   HIP_TRY(slab_sum_ex(g, P.slab, P.slabf, x, g->vmask.p, b, g->diag.p, omega, nullptr, nullptr, pxc ? y : nullptr));
   return GLS_OK;
 }
-}  // namespace
+}  // namespace gls_impl
+extern "C" {
 
 // y = A_s v with the operator the attached V-cycle smooths this level with (FP32 / Oseen per gls_mg_params)
 int gls_mg_smoother_apply(gls_ctx *c, const double *v, double *y) {
@@ -1809,899 +1826,7 @@ int gls_set_hanging(gls_ctx *c, int64_t n, const int64_t *dofs, const int64_t *o
   return detect_oct_bricks(c);
 }
 
-// --------------------------------------------------------------------------------------------
-// Geometric multigrid V-cycle (right preconditioner). Levels are nested hyper_cube meshes; the
-// coarse operators are the same GLS Jacobian re-discretised on the coarse mesh at the injected
-// state (Galerkin-free, matrix-free), smoothed by damped Jacobi on their own diagonals.
-// --------------------------------------------------------------------------------------------
 namespace {
-enum { MB_U = 0, MB_U1, MB_U2, MB_U3, MB_B, MB_X, MB_Y, MB_BOX, MB_N };
-constexpr int64_t kDirectSmall = 8192, kDirectMax = 40000;  // coarsest-level dense LU: FP64 / FP32 ranges
-double *mgbuf(gls_ctx *c, int l, int which) { return c->mg.bufs[(size_t)l * MB_N + which]->p; }
-int64_t mg_nbox(const gls_ctx *c, int l) {
-  const auto &d = c->mg.dims[(size_t)l];
-  return (int64_t)d[0] * d[1] * d[2];
-}
-// level-l local vector -> box lattice layout (identity on a single GPU: returns loc itself)
-const double *mg_to_box(gls_ctx *c, int l, const double *loc, bool owned_only) {
-  if (!c->mg.boxed) return loc;
-  gls_ctx *g = c->mg.lev[(size_t)l];
-  double *box = mgbuf(c, l, MB_BOX);
-  if (gls::mg_box_gather(loc, box, g->lat.map.p, mg_nbox(c, l), g->n_vnodes, owned_only ? g->dist.n_owned : -1,
-                         c->stream) != hipSuccess)
-    return nullptr;
-  return box;
-}
-// where a transfer writing level-l data must put it (the box buffer, or loc itself)
-double *mg_box_target(gls_ctx *c, int l, double *loc) { return c->mg.boxed ? mgbuf(c, l, MB_BOX) : loc; }
-int mg_from_box(gls_ctx *c, int l, double *loc) {
-  if (!c->mg.boxed) return GLS_OK;
-  gls_ctx *g = c->mg.lev[(size_t)l];
-  HIP_TRY(gls::mg_box_scatter(mgbuf(c, l, MB_BOX), loc, g->lat.map.p, mg_nbox(c, l), g->n_vnodes, c->stream));
-  return GLS_OK;
-}
-
-// injected coarse state (every second lattice node); history likewise
-int mg_inject_level(gls_ctx *c, int l, const double *fine, double *coarse) {
-  if (c->mg.csr) {  // general hierarchy: the fine value at each coarse DoF's position (hanging values follow)
-    const auto &X = *c->mg.xfer[(size_t)l - 1];
-    HIP_TRY(gls::vec_pack_dofs(fine, X.inj.p, X.nc, coarse, c->stream));
-    gls_ctx *g = c->mg.lev[(size_t)l];
-    if (g->hang.on)
-      HIP_TRY(gls::vec_csr_gather_set(coarse, coarse, g->hang.dof.p, g->hang.off.p, g->hang.master.p, g->hang.w.p,
-                                      (int64_t)g->hang.dof.n, c->stream));
-    return GLS_OK;
-  }
-  const double *fb = mg_to_box(c, l - 1, fine, false);
-  if (!fb) return set_err(GLS_EHIP, "mg box gather failed");
-  HIP_TRY(gls::mg_inject(fb, mg_box_target(c, l, coarse), c->mg.dims[(size_t)l - 1].data(), c->mg.dims[(size_t)l].data(),
-                         c->stream));
-  return mg_from_box(c, l, coarse);
-}
-
-int replica_gather(gls_ctx *c, const double *loc, double *glob);
-int rep2_inject(gls_ctx *c, const double *loc, double *glob);
-// The explicit coarse inverse (mg.probe) against the pinned matrix it came from (mg.probe_bak): y = A^-1 e,
-// z = A y for e = (1, ..., 1); good = y finite and max|z - e| <= 1e-8 max(1, max|A| max|y|) (a backward-stable
-// factorization leaves ~n eps there; an unpivoted LU through a tiny pivot leaves O(1) or non-finite values)
-static int coarse_inverse_check(gls_ctx *c, int64_t n, bool *good) {
-  auto &mg = c->mg;
-  *good = false;
-  if (mg.chk.n < (size_t)(2 * n)) GLS_TRY(mg.chk.alloc((size_t)(2 * n)));
-  double *y = mg.chk.p, *z = mg.chk.p + n;
-  HIP_TRY(gls::vec_fill(mg.unit.p, n, 1.0, c->stream));
-  const double one = 1.0, zero = 0.0;
-  rocblas_int imax = 0;
-  if (rocblas_set_stream(mg.blas, c->stream) != rocblas_status_success ||
-      rocblas_dgemv(mg.blas, rocblas_operation_none, (rocblas_int)n, (rocblas_int)n, &one, mg.probe.p, (rocblas_int)n,
-                    mg.unit.p, 1, &zero, y, 1) != rocblas_status_success ||
-      rocblas_dgemv(mg.blas, rocblas_operation_none, (rocblas_int)n, (rocblas_int)n, &one, mg.probe_bak.p,
-                    (rocblas_int)n, y, 1, &zero, z, 1) != rocblas_status_success ||
-      rocblas_idamax(mg.blas, (rocblas_int)(n * n), mg.probe_bak.p, 1, &imax) != rocblas_status_success)
-    return set_err(GLS_EHIP, "coarse inverse check: rocBLAS failed");
-  std::vector<double> h((size_t)(2 * n));
-  double amax = 0.0;
-  HIP_TRY(hipMemcpyAsync(h.data(), mg.chk.p, sizeof(double) * (size_t)(2 * n), hipMemcpyDeviceToHost, c->stream));
-  if (imax > 0)
-    HIP_TRY(hipMemcpyAsync(&amax, mg.probe_bak.p + (imax - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  double ymax = 0.0, err = 0.0;
-  for (int64_t i = 0; i < n; ++i) {
-    if (!std::isfinite(h[(size_t)i]) || !std::isfinite(h[(size_t)(n + i)])) return GLS_OK;
-    ymax = std::max(ymax, std::fabs(h[(size_t)i]));
-    err = std::max(err, std::fabs(h[(size_t)(n + i)] - 1.0));
-  }
-  *good = err <= 1e-8 * std::max(1.0, std::fabs(amax) * ymax);
-  if (std::getenv("GLS_MG_VERBOSE"))
-    std::printf("mg: coarse inverse check n=%lld max|Ay-e| %.3e max|A| %.3e max|y| %.3e -> %s\n", (long long)n, err,
-                std::fabs(amax), ymax, *good ? "ok" : "FAILED");
-  return GLS_OK;
-}
-
-// the direct coarse solve's matrix by colored probing on a per-cell level (mg.probe_ilu; brick levels and
-// distributed or nested contexts: one J.v per column): the ILU structure (CM order, fill 0, one block) is attached once
-int mg_probe_setup(gls_ctx *c, gls_ctx *g) {
-  auto &mg = c->mg;
-  mg.probe_ilu = nullptr;
-  if ((g->use_brick && g->use_qdata) || g->dist.on || g->mg.on || g->ilu.on)
-    return GLS_OK;
-  GLS_TRY(gls_ilu_set_options(g, GLS_ILU_ORDER_CM, 0));
-  GLS_TRY(gls_ilu_attach(g, 0, 0.0, 1.0));
-  g->ilu.probe_only = true;
-  mg.ilu_levels.push_back(g);  // detached with the multigrid
-  GLS_TRY(mg.pinv.alloc((size_t)g->n_dofs));
-  mg.probe_ilu = g;
-  return GLS_OK;
-}
-
-// the large coarsest level's FP32 factorization (kDirectSmall < n): rocSOLVER sgetrf_npvt of the pinned matrix (138 ms
-// at n = 25000 against sgetrf's 410 + sgetri's ~800) and its check |A x - 1| / |1| on the side stream, ordered after
-// the context stream's probing / rounding; nothing here waits on the host
-int coarse_lu32_start(gls_ctx *c, int64_t n, int64_t pin) {
-  auto &mg = c->mg;
-  HIP_TRY(mg.side.ensure());
-  hipStream_t s = mg.side.s;
-  if (mg.chk32.n != (size_t)(2 * n)) GLS_TRY(mg.chk32.alloc((size_t)(2 * n)));
-  if (mg.lu_rel.n != 1) GLS_TRY(mg.lu_rel.alloc(1));
-  HIP_TRY(hipEventRecord(mg.side.e0, c->stream));
-  HIP_TRY(hipStreamWaitEvent(s, mg.side.e0, 0));
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  mg.side.join();
-  mg.side.rc = 0;
-  auto *m = &mg;
-  const bool verbose = std::getenv("GLS_MG_VERBOSE") != nullptr;
-  const int64_t bl = mg.lu_cm ? mg.lu_bl : -1, bu = mg.lu_cm ? mg.lu_bu : -1;
-  mg.side.worker = std::thread([m, s, n, pin, dev, verbose, bl, bu]() {
-    const double one = 1.0, mone = -1.0;
-    int &rc = m->side.rc;
-    const auto h0 = std::chrono::steady_clock::now();
-    // banded: right-looking by column blocks as wide as the band (rocSOLVER's calls return only when done, so few
-    // wide blocks: 256-wide ones took 98 calls and longer than the dense factorization, profiles/
-    // r06_ab_banded_coarse_lu.txt): the block's panel down to the lower band, its rows of U to the upper band, the
-    // trailing band update; without pivoting nothing outside the band fills
-    const int64_t nb = bl < 0 ? n : std::max<int64_t>(512, ((std::max(bl, bu) + 255) / 256) * 256);
-    if (hipSetDevice(dev) != hipSuccess) rc = 1;
-    else if (rocblas_set_stream(m->blas, s) != rocblas_status_success) rc = 2;
-    const float fone = 1.0f, fmone = -1.0f;
-    float *A = m->probe32.p;
-    for (int64_t k0 = 0; k0 < n && !rc; k0 += nb) {
-      const int64_t kb = std::min(nb, n - k0), mr = bl < 0 ? n - k0 : std::min(n - k0, kb + bl);
-      const int64_t nc = bl < 0 ? 0 : std::min(n - k0 - kb, bu);
-      float *A11 = A + k0 + k0 * n, *A12 = A + k0 + (k0 + kb) * n;
-      if (rocsolver_sgetrf_npvt(m->blas, (rocblas_int)mr, (rocblas_int)kb, A11, (rocblas_int)n, m->info.p) !=
-          rocblas_status_success)
-        rc = 3;
-      else if (nc > 0 &&
-               rocblas_strsm(m->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_unit,
-                             (rocblas_int)kb, (rocblas_int)nc, &fone, A11, (rocblas_int)n, A12, (rocblas_int)n) !=
-                   rocblas_status_success)
-        rc = 3;
-      else if (nc > 0 && mr > kb &&
-               rocblas_sgemm(m->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)(mr - kb),
-                             (rocblas_int)nc, (rocblas_int)kb, &fmone, A11 + kb, (rocblas_int)n, A12, (rocblas_int)n,
-                             &fone, A12 + kb, (rocblas_int)n) != rocblas_status_success)
-        rc = 3;
-    }
-    if (verbose)
-      std::printf("mg: the %s FP32 LU returned to its worker thread after %.2f ms\n", bl < 0 ? "dense" : "banded",
-                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count());
-    if (!rc &&
-        !(gls::vec_fill(m->chk32.p, n, 1.0, s) == hipSuccess && gls::mg_zero_row(m->chk32.p, 1, pin, s) == hipSuccess &&
-          gls::vec_to_f32(m->chk32.p, m->x32.p, n, s) == hipSuccess &&
-          gls::dense_lu_solve_f32(m->probe32.p, (int)n, m->x32.p, s, (int)bl, (int)bu) == hipSuccess &&
-          gls::vec_from_f32(m->x32.p, m->chk32.p + n, n, s) == hipSuccess &&
-          rocblas_dgemv(m->blas, rocblas_operation_none, (rocblas_int)n, (rocblas_int)n, &one, m->probe.p,
-                        (rocblas_int)n, m->chk32.p + n, 1, &mone, m->chk32.p, 1) == rocblas_status_success &&
-          rocblas_set_pointer_mode(m->blas, rocblas_pointer_mode_device) == rocblas_status_success &&
-          rocblas_dnrm2(m->blas, (rocblas_int)n, m->chk32.p, 1, m->lu_rel.p) == rocblas_status_success))
-      rc = 4;
-    (void)rocblas_set_pointer_mode(m->blas, rocblas_pointer_mode_host);
-    if (!rc && hipEventRecord(m->side.e1, s) != hipSuccess) rc = 5;
-  });
-  mg.lu_pending = true;
-  mg.lu_n = n;
-  mg.lu_pin = pin;
-  return GLS_OK;
-}
-// before the first coarse solve of the state: the side stream's factorization checked; a factorization that pivot growth
-// broke (O(1) or non-finite residual) is replaced by the pivoted sgetrf + sgetri inverse on the context stream. A
-// coarse-grid correction accurate to 1 % is exact enough for the V-cycle.
-int coarse_lu32_finish(gls_ctx *c) {
-  auto &mg = c->mg;
-  if (!mg.lu_pending) return GLS_OK;
-  mg.lu_pending = false;
-  mg.side.join();
-  (void)rocblas_set_stream(mg.blas, c->stream);
-  if (mg.side.rc) {
-    mg.direct_ok = mg.lu32 = false;
-    mg.dirty = true;
-    return set_err(GLS_EHIP, "coarse FP32 LU on the side stream failed (step %d)", mg.side.rc);
-  }
-  const int64_t n = mg.lu_n;
-  int inf = -1;
-  double rn = INFINITY;
-  HIP_TRY(hipMemcpyAsync(&inf, mg.info.p, sizeof(int), hipMemcpyDeviceToHost, mg.side.s));
-  HIP_TRY(hipMemcpyAsync(&rn, mg.lu_rel.p, sizeof(double), hipMemcpyDeviceToHost, mg.side.s));
-  HIP_TRY(hipStreamSynchronize(mg.side.s));
-  const double rel = inf == 0 ? rn / std::sqrt((double)n) : INFINITY;
-  const bool verbose = std::getenv("GLS_MG_VERBOSE") != nullptr;
-  // (below 1e-2 the correction is used as it is; up to 0.5 with one refinement step x += LU^-1 (b - A x) against the
-  // FP64 matrix (an extra solve and one FP64 matrix pass per coarse solve: residual error ~ rel^2); beyond, or a
-  // broken factorization, the pivoted route)
-  mg.lu32_refine = inf == 0 && rel >= 1e-2 && rel < 0.5;
-  if (verbose)
-    std::printf("mg: coarse FP32 unpivoted LU n=%lld info=%d, check |A x - 1| / |1| = %.2e%s\n", (long long)n, inf, rel,
-                mg.lu32_refine ? ", applied with one refinement step" : "");
-  if (inf == 0 && rel < 0.5) return GLS_OK;
-  mg.lu32_npvt = mg.lu32_refine = false;
-  HIP_TRY(gls::vec_to_f32(mg.probe.p, mg.probe32.p, n * n, c->stream));  // the pinned matrix again
-  if (rocblas_set_stream(mg.blas, c->stream) != rocblas_status_success ||
-      rocsolver_sgetrf(mg.blas, (rocblas_int)n, (rocblas_int)n, mg.probe32.p, (rocblas_int)n, mg.ipiv.p, mg.info.p) !=
-          rocblas_status_success)
-    return set_err(GLS_EHIP, "rocsolver_sgetrf failed");
-  HIP_TRY(hipMemcpyAsync(&inf, mg.info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (inf == 0) {
-    if (rocsolver_sgetri(mg.blas, (rocblas_int)n, mg.probe32.p, (rocblas_int)n, mg.ipiv.p, mg.info.p) !=
-        rocblas_status_success)
-      return set_err(GLS_EHIP, "rocsolver_sgetri failed");
-    HIP_TRY(hipMemcpyAsync(&inf, mg.info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  if (verbose) std::printf("mg: coarse FP32 pivoted LU + inverse n=%lld info=%d\n", (long long)n, inf);
-  if (inf != 0) {
-    mg.direct_ok = mg.lu32 = false;
-    mg.dirty = true;
-    return set_err(GLS_EINVAL, "coarse FP32 LU: zero pivot %d", inf);
-  }
-  return GLS_OK;
-}
-
-int mg_prepare(gls_ctx *c) {
-  auto &mg = c->mg;
-  if (!mg.dirty) return GLS_OK;
-  GLS_TRY(coarse_lu32_finish(c));  // (its buffers are re-probed below)
-  const bool verbose = std::getenv("GLS_MG_VERBOSE") != nullptr;
-  auto tick = [&]() {  // host wall time of the preparation phases (verbose only: synchronizes)
-    if (verbose) (void)hipStreamSynchronize(c->stream);
-    return std::chrono::steady_clock::now();
-  };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
-  };
-  const auto t0 = tick();
-  const int L = (int)mg.lev.size();
-  // the levels are re-discretised at the Jacobian's state (the frozen snapshot under skip_newton)
-  const bool fz = c->jf.on;
-  const double *ju = fz ? c->jf.u.p : c->u;
-  const double *jh[3] = {fz ? (c->jf.has[0] ? c->jf.h[0].p : nullptr) : c->u1,
-                         fz ? (c->jf.has[1] ? c->jf.h[1].p : nullptr) : c->u2,
-                         fz ? (c->jf.has[2] ? c->jf.h[2].p : nullptr) : c->u3};
-  const int jscheme = fz ? c->jf.scheme : c->scheme;
-  const double *jts = fz ? c->jf.ts : c->time_steps;
-  for (int l = 1; l < L; ++l) {
-    gls_ctx *g = mg.lev[l];
-    const double *fu = l == 1 ? ju : mgbuf(c, l - 1, MB_U);
-    const double *fh[3] = {l == 1 ? jh[0] : (jh[0] ? mgbuf(c, l - 1, MB_U1) : nullptr),
-                           l == 1 ? jh[1] : (jh[1] ? mgbuf(c, l - 1, MB_U2) : nullptr),
-                           l == 1 ? jh[2] : (jh[2] ? mgbuf(c, l - 1, MB_U3) : nullptr)};
-    GLS_TRY(mg_inject_level(c, l, fu, mgbuf(c, l, MB_U)));
-    GLS_TRY(gls_apply_dirichlet(g, mgbuf(c, l, MB_U)));
-    double *gh[3] = {nullptr, nullptr, nullptr};
-    for (int h = 0; h < 3; ++h)
-      if (fh[h]) {
-        gh[h] = mgbuf(c, l, MB_U1 + h);
-        GLS_TRY(mg_inject_level(c, l, fh[h], gh[h]));
-      }
-    g->viscosity = c->viscosity;
-    GLS_TRY(gls_set_time(g, jscheme, jts));
-    GLS_TRY(gls_set_state(g, mgbuf(c, l, MB_U), gh[0], gh[1], gh[2]));
-    GLS_TRY(ensure_diag(g));
-  }
-  if (mg.rep_csr) {  // the replica hierarchy takes the fine state (injected, summed over ranks) and time data
-    gls_ctx *r = mg.rep2;
-    const double *st[4] = {ju, jh[0], jh[1], jh[2]};
-    for (int i = 0; i < 4; ++i)
-      if (st[i]) GLS_TRY(rep2_inject(c, st[i], mg.rep_u[i].p));
-    GLS_TRY(gls_apply_dirichlet(r, mg.rep_u[0].p));
-    r->viscosity = c->viscosity;
-    GLS_TRY(gls_set_time(r, jscheme, jts));
-    GLS_TRY(gls_set_state(r, mg.rep_u[0].p, st[1] ? mg.rep_u[1].p : nullptr, st[2] ? mg.rep_u[2].p : nullptr,
-                          st[3] ? mg.rep_u[3].p : nullptr));
-    if (!mg.direct) {
-      mg.dirty = false;
-      return GLS_OK;
-    }
-  }
-  if (mg.replica) {  // the replica takes the coarsest distributed level's state (gathered) and time data
-    gls_ctx *g = mg.lev[(size_t)L - 1], *r = mg.replica;
-    const double *st[4] = {g->u, g->u1, g->u2, g->u3};
-    for (int i = 0; i < 4; ++i)
-      if (st[i]) GLS_TRY(replica_gather(c, st[i], mg.rep_u[i].p));
-    r->viscosity = c->viscosity;
-    GLS_TRY(gls_set_time(r, jscheme, jts));
-    GLS_TRY(gls_set_state(r, mg.rep_u[0].p, st[1] ? mg.rep_u[1].p : nullptr, st[2] ? mg.rep_u[2].p : nullptr,
-                          st[3] ? mg.rep_u[3].p : nullptr));
-  }
-  mg.direct_ok = false;
-  if (mg.direct) {  // probe A = J_coarse column by column, then invert on the device
-    // coarsest level: the last one, or the whole-mesh replica below a distributed fine level (rep_csr)
-    gls_ctx *g = mg.rep_csr ? mg.rep2 : mg.lev[(size_t)L - 1];
-    const int64_t n = g->n_dofs;
-    if (g->use_brick && g->use_qdata) {  // all unit vectors in one launch per batch
-      GLS_TRY(ensure_diag(g));
-      GLS_TRY(ensure_qdata(g));
-      gls::OpParams P = make_params(g, true);
-      P.qd = g->qdata.p;
-      P.y = mg.probe.p;
-      HIP_TRY(hipMemsetAsync(mg.probe.p, 0, sizeof(double) * (size_t)(n * n), c->stream));
-      const int batch = 4096;
-      for (int64_t j0 = 0; j0 < n; j0 += batch) {
-        const int nb = (int)std::min<int64_t>(batch, n - j0);
-        P.y = mg.probe.p + j0 * n;
-        HIP_TRY(gls::launch_brick_probe(g->k, P, g->tables, j0, nb, c->stream));
-        HIP_TRY(gls::mg_probe_fix(mg.probe.p + j0 * n, n, j0, nb, g->con_dofs.p, (int64_t)g->con_dofs.n, g->diag.p,
-                                  c->stream));
-      }
-    } else if (mg.probe_ilu == g && g->ilu.on) {  // colored batched probes into the ILU's CSR, then dense
-      GLS_TRY(ensure_diag(g));
-      GLS_TRY(ilu_probe(g));
-      HIP_TRY(hipMemsetAsync(mg.probe.p, 0, sizeof(double) * (size_t)(n * n), c->stream));
-      const auto &I = g->ilu;
-      mg.lu_cm = n > kDirectSmall;
-      if (mg.lu_cm) {  // FP32 range: keep the CSR's Cuthill-McKee order (banded), bandwidths from its pattern once
-        if (mg.lu_bl < 0) {
-          std::vector<int64_t> rp((size_t)n + 1);
-          std::vector<int32_t> cl((size_t)I.nnz), pm((size_t)n), id((size_t)n);
-          HIP_TRY(hipMemcpy(rp.data(), I.rowp.p, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost));
-          HIP_TRY(hipMemcpy(cl.data(), I.col.p, sizeof(int32_t) * cl.size(), hipMemcpyDeviceToHost));
-          HIP_TRY(hipMemcpy(pm.data(), I.perm.p, sizeof(int32_t) * pm.size(), hipMemcpyDeviceToHost));
-          int64_t bl = 0, bu = 0;
-          for (int64_t r = 0; r < n; ++r)
-            for (int64_t e = rp[(size_t)r]; e < rp[(size_t)r + 1]; ++e) {
-              bl = std::max<int64_t>(bl, r - cl[(size_t)e]);
-              bu = std::max<int64_t>(bu, cl[(size_t)e] - r);
-            }
-          for (int64_t i = 0; i < n; ++i) id[(size_t)i] = (int32_t)i;
-          GLS_TRY(mg.lu_ident.upload(id.data(), id.size()));
-          GLS_TRY(mg.lu_tmp.alloc((size_t)n));
-          mg.lu_bl = bl;
-          mg.lu_bu = bu;
-          mg.lu_pin_cm = pm[(size_t)((int64_t)g->dim * g->n_vnodes)];  // the first pressure DoF's row
-          if (verbose) std::printf("mg: coarse matrix n=%lld in Cuthill-McKee order: bandwidths %lld / %lld\n", (long long)n,
-                                   (long long)bl, (long long)bu);
-        }
-        HIP_TRY(gls::csr_to_dense(mg.probe.p, I.rowp.p, I.col.p, I.val.p, mg.lu_ident.p, mg.pinv.p, n, c->stream));
-      } else {
-        HIP_TRY(gls::csr_to_dense(mg.probe.p, I.rowp.p, I.col.p, I.val.p, I.perm.p, mg.pinv.p, n, c->stream));
-      }
-    } else {
-      HIP_TRY(gls::vec_fill(mg.unit.p, n, 0.0, c->stream));
-      for (int64_t j = 0; j < n; ++j) {
-        HIP_TRY(gls::mg_unit_step(mg.unit.p, j, c->stream));
-        GLS_TRY(gls_jacobian_apply(g, mg.unit.p, mg.probe.p + j * n));
-      }
-    }
-    const auto t1 = tick();
-    mg.lu = false;
-    mg.lu32 = false;
-    if (n > kDirectSmall) {  // FP32 LU of the pinned matrix: unpivoted (checked), else pivoted + explicit inverse
-      const int64_t pin0 = (int64_t)g->dim * g->n_vnodes;  // the first pressure DoF
-      if (pin0 >= n) return set_err(GLS_EINVAL, "mg: coarsest level without pressure DoFs");
-      if (!(mg.probe_ilu == g && g->ilu.on)) mg.lu_cm = false;
-      const int64_t pin = mg.lu_cm ? mg.lu_pin_cm : pin0;  // (its row in the matrix's order)
-      HIP_TRY(gls::mg_pin_dof(mg.probe.p, n, pin, c->stream));
-      HIP_TRY(gls::vec_to_f32(mg.probe.p, mg.probe32.p, n * n, c->stream));
-      GLS_TRY(coarse_lu32_start(c, n, pin));
-      if (verbose) std::printf("mg: coarse FP32 unpivoted LU n=%lld queued on the side stream at %.2f ms\n", (long long)n,
-                               ms(t0, tick()));
-      mg.lu32 = mg.lu32_npvt = mg.direct_ok = true;
-      mg.dirty = false;
-      return GLS_OK;
-    }
-    // gj | lu | lu_npvt. Default: LU without pivoting (rocSOLVER's pivoted panel factorization is ~1 ms of
-    // a Newton step at n = 500, profiles/r04_ab_env_switches.txt) with a pivoted retry when a pivot vanishes
-    const char *cs = std::getenv("GLS_MG_COARSE_SOLVER");
-    const bool use_lu = cs ? std::strncmp(cs, "lu", 2) == 0 : true;  // LU: 1.5-3 ms at n = 500 vs the one-workgroup GJ's ~15
-    bool npvt = cs ? std::strcmp(cs, "lu_npvt") == 0 : true;
-    if (use_lu) {  // LU with the pressure gauge pinned
-      const int64_t pin = (int64_t)g->dim * g->n_vnodes;  // the first pressure DoF
-      if (pin >= n) return set_err(GLS_EINVAL, "mg: coarsest level without pressure DoFs");
-      HIP_TRY(gls::mg_pin_dof(mg.probe.p, n, pin, c->stream));
-      if (npvt && !cs) {  // keep the matrix for a pivoted retry
-        if (mg.probe_bak.n != (size_t)(n * n)) GLS_TRY(mg.probe_bak.alloc((size_t)(n * n)));
-        HIP_TRY(gls::vec_copy(mg.probe_bak.p, mg.probe.p, n * n, c->stream));
-      }
-      int inf = -1;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        if (rocblas_set_stream(mg.blas, c->stream) != rocblas_status_success ||
-            (npvt ? rocsolver_dgetrf_npvt(mg.blas, (rocblas_int)n, (rocblas_int)n, mg.probe.p, (rocblas_int)n, mg.info.p)
-                  : rocsolver_dgetrf(mg.blas, (rocblas_int)n, (rocblas_int)n, mg.probe.p, (rocblas_int)n, mg.ipiv.p,
-                                     mg.info.p)) != rocblas_status_success)
-          return set_err(GLS_EHIP, "rocsolver_dgetrf failed");
-        if (npvt) {  // identity permutation for getri
-          if (mg.npvt_ipiv_n != n) {
-            std::vector<int> id((size_t)n);
-            for (int64_t i = 0; i < n; ++i) id[(size_t)i] = (int)(i + 1);
-            HIP_TRY(hipMemcpyAsync(mg.ipiv.p, id.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            mg.npvt_ipiv_n = n;
-          }
-        }
-        HIP_TRY(hipMemcpyAsync(&inf, mg.info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (inf == 0 || !npvt || cs) break;
-        if (verbose) std::printf("mg: unpivoted coarse LU hit pivot %d, retrying with pivoting\n", inf);
-        HIP_TRY(gls::vec_copy(mg.probe.p, mg.probe_bak.p, n * n, c->stream));  // the pinned matrix again
-        npvt = false;
-        mg.npvt_ipiv_n = -1;  // getrf overwrites ipiv with its permutation
-      }
-      const auto t2 = tick();
-      if (verbose) std::printf("mg: levels+probe %.2f ms, getrf %.2f ms\n", ms(t0, t1), ms(t1, t2));
-      if (inf == 0) {
-        if (rocsolver_dgetri(mg.blas, (rocblas_int)n, mg.probe.p, (rocblas_int)n, mg.ipiv.p, mg.info.p) !=
-            rocblas_status_success)
-          return set_err(GLS_EHIP, "rocsolver_dgetri failed");
-        HIP_TRY(hipMemcpyAsync(&inf, mg.info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        // an unpivoted LU of the indefinite velocity-pressure Jacobian passes getrf with a tiny nonzero
-        // pivot and can return a wildly wrong (or non-finite) inverse: check A (A^-1 e) = e and redo the
-        // factorization with partial pivoting when it fails
-        if (inf == 0 && npvt && !cs) {
-          bool good = false;
-          GLS_TRY(coarse_inverse_check(c, n, &good));
-          if (!good) {
-            if (verbose) std::printf("mg: unpivoted coarse inverse failed its check, refactoring with pivoting\n");
-            HIP_TRY(gls::vec_copy(mg.probe.p, mg.probe_bak.p, n * n, c->stream));
-            mg.npvt_ipiv_n = -1;
-            npvt = false;
-            if (rocsolver_dgetrf(mg.blas, (rocblas_int)n, (rocblas_int)n, mg.probe.p, (rocblas_int)n, mg.ipiv.p,
-                                 mg.info.p) != rocblas_status_success)
-              return set_err(GLS_EHIP, "rocsolver_dgetrf failed");
-            HIP_TRY(hipMemcpyAsync(&inf, mg.info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (inf == 0) {
-              if (rocsolver_dgetri(mg.blas, (rocblas_int)n, mg.probe.p, (rocblas_int)n, mg.ipiv.p, mg.info.p) !=
-                  rocblas_status_success)
-                return set_err(GLS_EHIP, "rocsolver_dgetri failed");
-              HIP_TRY(hipMemcpyAsync(&inf, mg.info.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-              HIP_TRY(hipStreamSynchronize(c->stream));
-            }
-          }
-        }
-        if (inf == 0) HIP_TRY(gls::mg_zero_row(mg.probe.p, n, pin, c->stream));  // pinned unknown: zero correction
-      }
-      mg.lu = mg.direct_ok = inf == 0;
-      if (verbose) std::printf("mg: coarse LU n=%lld info=%d, getri done at %.2f ms\n", (long long)n, inf, ms(t0, tick()));
-      if (!mg.lu) {  // re-probe for the Gauss-Jordan fallback below (getrf overwrote the matrix)
-        mg.dirty = true;
-        return set_err(GLS_EINVAL, "coarse LU: zero pivot %d (set GLS_MG_COARSE_SOLVER=gj)", inf);
-      }
-    } else {
-      HIP_TRY(gls::mg_dense_invert(mg.probe.p, mg.aug.p, (int)n, mg.status.p, c->stream));
-      int st = -1;
-      HIP_TRY(hipMemcpyAsync(&st, mg.status.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      // a couple of dependent columns (pressure gauge) are expected; many mean a broken operator
-      mg.direct_ok = st >= 0 && st <= 4;
-      if (std::getenv("GLS_MG_VERBOSE")) std::printf("mg: coarse direct solve n=%lld dropped=%d ok=%d\n", (long long)n, st, (int)mg.direct_ok);
-    }
-  }
-  mg.dirty = false;
-  return GLS_OK;
-}
-
-// coarse rhs bc (level l+1) = R y (y on level l): restrict the owned rows, export-add coarse ghost rows
-int mg_restrict(gls_ctx *c, int l, const double *y, double *bc) {
-  auto &mg = c->mg;
-  gls_ctx *h = mg.lev[(size_t)l + 1];
-  hipStream_t s = c->stream;
-  if (mg.csr) {
-    const auto &X = *mg.xfer[(size_t)l];
-    HIP_TRY(gls::vec_csr_spmv(bc, y, X.roff.p, X.rcol.p, X.rw.p, X.nc, false, s, X.rlane));
-    (void)h;
-    return GLS_OK;
-  }
-  const double *yb = mg_to_box(c, l, y, true);
-  if (!yb) return set_err(GLS_EHIP, "mg box gather failed");
-  {
-    const auto &T = *mg.taps[(size_t)l];
-    const int32_t *ti[3] = {T.ri[0].p, T.ri[1].p, T.ri[2].p}, *tc[3] = {T.rc[0].p, T.rc[1].p, T.rc[2].p};
-    const double *tw[3] = {T.rw[0].p, T.rw[1].p, T.rw[2].p};
-    if (T.two_pass)
-      HIP_TRY(gls::mg_transfer_2pass(yb, mg_box_target(c, l + 1, bc), mg.dims[l].data(), mg.dims[l + 1].data(), 1, ti,
-                                     tw, tc, mg.xwork.p, s));
-    else
-      HIP_TRY(gls::mg_transfer3d(yb, mg_box_target(c, l + 1, bc), mg.dims[l].data(), mg.dims[l + 1].data(), ti, tw,
-                                 tc, s));
-  }
-  GLS_TRY(mg_from_box(c, l + 1, bc));
-  GLS_TRY(dist_export_add(h, bc));
-  return GLS_OK;
-}
-
-// y (level l) = P xc (xc on level l+1; its ghost values are imported first); add: y += P xc
-// (single rank, two-pass transfer only: the caller checks mg_prolong_add_ok)
-bool mg_prolong_add_ok(gls_ctx *c, int l) {
-  if (c->mg.csr) return false;  // general hierarchies: P xc, constrained rows zeroed, then added
-  return !c->mg.boxed && c->mg.taps[(size_t)l]->two_pass && std::getenv("GLS_MG_NO_FUSE") == nullptr;
-}
-int mg_prolong(gls_ctx *c, int l, double *xc, double *y, bool add = false) {
-  auto &mg = c->mg;
-  gls_ctx *h = mg.lev[(size_t)l + 1];
-  hipStream_t s = c->stream;
-  if (mg.csr) {
-    const auto &X = *mg.xfer[(size_t)l];
-    HIP_TRY(gls::vec_csr_spmv(y, xc, X.poff.p, X.pcol.p, X.pw.p, X.nf, add, s, X.plane));
-    return GLS_OK;
-  }
-  GLS_TRY(dist_import(h, xc));
-  const double *xb = mg_to_box(c, l + 1, xc, false);
-  if (!xb) return set_err(GLS_EHIP, "mg box gather failed");
-  {
-    const auto &T = *mg.taps[(size_t)l];
-    const int32_t *ti[3] = {T.pi[0].p, T.pi[1].p, T.pi[2].p}, *tc[3] = {T.pc[0].p, T.pc[1].p, T.pc[2].p};
-    const double *tw[3] = {T.pw[0].p, T.pw[1].p, T.pw[2].p};
-    if (T.two_pass)
-      HIP_TRY(gls::mg_transfer_2pass(xb, mg_box_target(c, l, y), mg.dims[l + 1].data(), mg.dims[l].data(), 0, ti, tw,
-                                     tc, mg.xwork.p, s, add ? 1 : 0));
-    else if (add)
-      return set_err(GLS_EINVAL, "mg_prolong: accumulate needs the two-pass transfer");
-    else
-      HIP_TRY(gls::mg_transfer3d(xb, mg_box_target(c, l, y), mg.dims[l + 1].data(), mg.dims[l].data(), ti, tw, tc, s));
-  }
-  GLS_TRY(mg_from_box(c, l, y));
-  return GLS_OK;
-}
-
-// The residual and its restriction in one J.v launch (single rank, FP32 smoothing on the cube's Q2 bricks,
-// nested lattice levels with the two-pass taps): the pencil J.v restricts each brick's part of b - A x to the
-// brick's coarse cell, and one sum over the coarse lattice forms the coarse right-hand side with its constrained
-// rows zeroed. The fine residual vector, the slab, its sum and both restriction passes are not needed.
-// GLS_MG_FUSE_TRANSFER=0 (read per call) or GLS_MG_NO_FUSE keep the separate launches.
-bool mg_fused_restrict_ok(gls_ctx *c, int l) {
-  auto &mg = c->mg;
-  if (l < 0 || l + 1 >= (int)mg.lev.size() || mg.csr || mg.boxed || (size_t)l >= mg.taps.size()) return false;
-  const char *e = std::getenv("GLS_MG_FUSE_TRANSFER");
-  if ((e && std::atoi(e) == 0) || std::getenv("GLS_MG_NO_FUSE") != nullptr) return false;
-  gls_ctx *g = mg.lev[(size_t)l], *h = mg.lev[(size_t)l + 1];
-  const auto &T = *mg.taps[(size_t)l];
-  const int64_t nc1 = 2 * (int64_t)g->cube_nb1 + 1;
-  return T.two_pass && T.q2_brick && g->smooth_f32 && g->use_brick && g->use_qdata && !g->use_colors && !g->dist.on &&
-         !g->hang.on && !g->oct.on && g->k == 2 && g->cube_nb1 > 0 && g->cube_nb1 < 1024 && g->use_slab && !g->srf &&
-         gls::pencil_enabled() && gls::brick_fused_jacobi_supported(g->k) && !h->dist.on && !h->hang.on &&
-         h->n_vnodes == nc1 * nc1 * nc1 && g->stream == c->stream;
-}
-// bc (level l + 1) = R (b - A x) with the constrained coarse rows zeroed (x, b on level l). first_omega > 0
-// (first_sweep_fusable levels): x is not read but formed and stored as the first damped-Jacobi sweep from 0,
-// as in jacobian_apply_f32
-int mg_residual_restrict_fused(gls_ctx *c, int l, double *x, const double *b, double *bc, double first_omega = 0.0) {
-  gls_ctx *g = c->mg.lev[(size_t)l], *h = c->mg.lev[(size_t)l + 1];
-  if (!g->u) return set_err(GLS_EINVAL, "gls_set_state was not called");
-  GLS_TRY(ensure_diag(g));
-  GLS_TRY(ensure_qdata32(g, !g->smooth_oseen));
-  gls::OpParams P = make_params(g, true);
-  P.qdf = g->qdata32.p;
-  P.oseen = g->smooth_oseen ? 1 : 0;
-  P.v = x;
-  P.rb = b;
-  P.cube_nb1 = g->cube_nb1;
-  if (first_omega > 0.0) {
-    P.jx0 = x;
-    P.jd = g->diag.p;
-    P.jomega = first_omega;
-  }
-  P.slab = brick_slab(g);  // holds the bricks' coarse element vectors [brick][27][4] here (the slab is larger)
-  if (!P.slab) return set_err(GLS_EHIP, "brick slab allocation failed");
-  {
-    TimedLaunch t(g, 4);
-    HIP_TRY(gls::launch_pencil_jv_restrict(P, g->tables, c->stream));
-  }
-  TimedLaunch t(g, 5);
-  HIP_TRY(gls::brick_restrict_sum_cube(g->cube_nb1, P.slab, h->n_vnodes, bc, h->vmask.p, c->stream));
-  return GLS_OK;
-}
-
-// The prolongation inside the first post-sweep (same level pairs as the fused restriction, and the coarse level a
-// verified hyper_cube lattice too): the fused damped-Jacobi sweep's J.v gathers x + P xc, interpolating each
-// brick's coarse cell in LDS, and hands that value at the brick-surface nodes to the slab sum through the level's
-// scratch vector, so the two transfer launches and their passes over x are not needed. The hard-coded Q2 weights are those checked against the level
-// pair's tap tables at attach (Taps::q2_brick). GLS_MG_FUSE_PROLONG=0 (read per call) or GLS_MG_NO_FUSE keep the
-// separate launches.
-bool mg_fused_prolong_ok(gls_ctx *c, int l) {
-  auto &mg = c->mg;
-  if (l < 0 || l + 1 >= (int)mg.lev.size() || mg.csr || mg.boxed || (size_t)l >= mg.taps.size() || !mg_prolong_add_ok(c, l))
-    return false;
-  const char *e = std::getenv("GLS_MG_FUSE_PROLONG");
-  if (e && std::atoi(e) == 0) return false;
-  gls_ctx *g = mg.lev[(size_t)l], *h = mg.lev[(size_t)l + 1];
-  const auto &T = *mg.taps[(size_t)l];
-  const int64_t nc1 = 2 * (int64_t)g->cube_nb1 + 1;
-  const bool ilu_smooth = mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only;
-  return T.two_pass && T.q2_brick && mg.lpost[(size_t)l] >= 1 && !ilu_smooth && g->smooth_f32 && g->use_brick &&
-         g->use_qdata && !g->use_colors && !g->dist.on && !g->hang.on && !g->oct.on && g->k == 2 && g->cube_nb1 > 0 &&
-         g->cube_nb1 < 1024 && g->use_slab && brick_slab(g) && !g->srf && gls::pencil_enabled() &&
-         gls::brick_fused_jacobi_supported(g->k) && !h->dist.on && !h->hang.on && h->cube_nb1 > 0 &&
-         g->cube_nb1 == 2 * h->cube_nb1 && h->n_vnodes == nc1 * nc1 * nc1 && g->stream == c->stream;
-}
-
-// coarsest level by HIP graph (opt-in, GLS_MG_GRAPH=1: measured at 128^3, 138.0 vs 138.6 ms per
-// Newton step -- the coarse sweeps are bound by the kernels' own latency, not by launch overhead,
-// profiles/r01_coarse_graph_bench.txt): one rank, fused brick sweeps, the level's own b / x buffers (the
-// captured launches bake in their pointers and this state's OpParams; mg_prepare drops the graph)
-bool coarse_graph_eligible(gls_ctx *c, gls_ctx *g, const double *b, const double *x) {
-  const int l = (int)c->mg.lev.size() - 1;
-  return !c->mg.cgraph_failed && !c->mg.boxed && !g->dist.on && !g->hang.on && g->use_brick && g->use_qdata &&
-         brick_slab(g) && gls::brick_fused_jacobi_supported(g->k) && g->stream == c->stream &&
-         b == mgbuf(c, l, MB_B) && x == mgbuf(c, l, MB_X) && std::getenv("GLS_MG_NO_FUSE") == nullptr &&
-         std::getenv("GLS_MG_GRAPH") != nullptr;
-}
-// everything the captured launches bake in: the level's OpParams (pointers, time coefficients,
-// viscosity), the sweep count and damping, and the buffers the sweeps read and write. Buffer
-// CONTENTS (state, linearization, diagonal) are read at replay time, so a new Newton state with
-// unchanged parameters replays the same graph.
-}  // extern "C"
-static std::vector<unsigned char> coarse_graph_key(gls_ctx *g, const double *b, const double *x, const double *y,
-                                                   int pre, double om) {
-  const gls::OpParams P = make_params(g);
-  const void *ptrs[7] = {b, x, y, g->diag.p, g->qdata.p, g->qdata32.p, brick_slab(g)};
-  const int64_t ints[4] = {pre, g->n_dofs, (int64_t)g->smooth_f32, (int64_t)slab_f32()};
-  std::vector<unsigned char> k(sizeof(P) + sizeof(ptrs) + sizeof(ints) + sizeof(om));
-  unsigned char *o = k.data();
-  std::memcpy(o, &P, sizeof(P));
-  std::memcpy(o += sizeof(P), ptrs, sizeof(ptrs));
-  std::memcpy(o += sizeof(ptrs), ints, sizeof(ints));
-  std::memcpy(o + sizeof(ints), &om, sizeof(om));
-  return k;
-}
-extern "C" {
-// capture x = csweeps damped-Jacobi sweeps from x = 0 on c's stream; a refused capture leaves the
-// plain launches in place (cgraph_failed)
-int coarse_graph_capture(gls_ctx *c, gls_ctx *g, const double *b, double *x, double *y, int pre, double om) {
-  auto &mg = c->mg;
-  hipStream_t s = c->stream;
-  GLS_TRY(ensure_diag(g));
-  GLS_TRY(g->smooth_f32 ? ensure_qdata32(g, !g->smooth_oseen) : ensure_qdata(g));
-  if (g->use_colors && g->acc.n != (size_t)g->n_dofs) GLS_TRY(g->acc.alloc((size_t)g->n_dofs));  // no malloc in capture
-  const bool tim = g->timing;
-  g->timing = false;  // no event records inside the capture
-  hipGraph_t gr = nullptr;
-  int rc = GLS_OK;
-  hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-  if (e == hipSuccess) {
-    if (hipError_t e1 = gls::mg_jacobi_update(x, b, nullptr, g->diag.p, om, g->n_dofs, 1, s); e1 != hipSuccess)
-      e = e1;
-    for (int it = 1; it < pre && rc == GLS_OK && e == hipSuccess; ++it) rc = smoother_sweep(g, x, b, y, om);
-    const hipError_t e2 = hipStreamEndCapture(s, &gr);
-    if (e == hipSuccess) e = e2;
-  }
-  g->timing = tim;
-  hipGraphExec_t ex = nullptr;
-  if (rc == GLS_OK && e == hipSuccess && gr) e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
-  if (gr) (void)hipGraphDestroy(gr);
-  if (rc != GLS_OK || e != hipSuccess || !ex) {
-    (void)hipGetLastError();
-    if (ex) (void)hipGraphExecDestroy(ex);
-    mg.cgraph_failed = true;
-    if (std::getenv("GLS_MG_VERBOSE")) std::printf("mg: coarse graph capture refused (%s)\n", hipGetErrorString(e));
-    return GLS_OK;
-  }
-  mg.cgraph.h = ex;
-  mg.cgraph_key = coarse_graph_key(g, b, x, y, pre, om);
-  return GLS_OK;
-}
-
-// in-place sum over ranks of a device vector through c's transport (RCCL: one call; callback transports
-// through their reduction buffer in chunks of GLS_RED_BUF_MIN values)
-int dist_allreduce_vector(gls_ctx *c, double *v, int64_t n) {
-  auto &D = c->dist;
-  if (!D.on) return GLS_OK;
-  if (D.comm) {
-    if (D.allreduce(D.user, v, (int)n) != 0) return set_err(GLS_ECOMM, "vector all-reduce failed");
-    return GLS_OK;
-  }
-  hipStream_t s = c->stream;
-  for (int64_t o = 0; o < n; o += GLS_RED_BUF_MIN) {
-    const int len = (int)std::min<int64_t>(GLS_RED_BUF_MIN, n - o);
-    HIP_TRY(hipMemcpyAsync(D.red_buf, v + o, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
-    if (D.allreduce(D.user, D.red_buf, len) != 0) return set_err(GLS_ECOMM, "vector all-reduce failed");
-    HIP_TRY(hipMemcpyAsync(v + o, D.red_buf, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
-  }
-  return GLS_OK;
-}
-// the replica's copy of a fine-level state vector: each replica DoF takes its injection source's value on
-// the one rank that owns that fine DoF (0 elsewhere), then the sum over ranks
-int rep2_inject(gls_ctx *c, const double *loc, double *glob) {
-  auto &mg = c->mg;
-  const int64_t ng = mg.rep2->n_dofs, ni = (int64_t)mg.r2inj_c.n;
-  HIP_TRY(gls::vec_fill(glob, ng, 0.0, c->stream));
-  if (ni) {
-    HIP_TRY(gls::vec_pack_dofs(loc, mg.r2inj_f.p, ni, mg.rep_tmp.p, c->stream));
-    HIP_TRY(gls::vec_unpack_dofs(glob, mg.r2inj_c.p, ni, mg.rep_tmp.p, c->stream));
-  }
-  return dist_allreduce_vector(c, glob, ng);
-}
-// one V-cycle with the replica hierarchy below the distributed fine level (gls_mg_attach_replica)
-int mg_vcycle_rep2(gls_ctx *c, const double *b, double *x) {
-  auto &mg = c->mg;
-  gls_ctx *r = mg.rep2;
-  const int64_t n = c->n_dofs, ng = r->n_dofs;
-  hipStream_t s = c->stream;
-  GLS_TRY(ensure_diag(c));
-  double *y = mgbuf(c, 0, MB_Y);
-  double *zs = mg.ilu_smooth && c->ilu.on && !c->ilu.probe_only ? mgbuf(c, 0, MB_BOX) : nullptr;
-  const int pre = mg.lpre[0], post = mg.lpost[0];
-  if (pre > 0 && zs) {
-    GLS_TRY(ensure_ilu(c));
-    GLS_TRY(apply_ilu(c, b, x));
-    for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(c, x, b, y, mg.omega, zs));
-  } else if (pre > 0) {
-    HIP_TRY(gls::mg_jacobi_update(x, b, nullptr, c->diag.p, mg.omega, n, 1, s));
-    for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(c, x, b, y, mg.omega));
-  } else {
-    HIP_TRY(gls::vec_fill(x, n, 0.0, s));
-  }
-  if (pre > 0) GLS_TRY(smoother_apply(c, x, y, b));  // y = b - A x
-  else HIP_TRY(gls::vec_copy(y, b, n, s));
-  // restriction: the owned rows' part of P^T y on this rank, summed over ranks
-  HIP_TRY(gls::vec_csr_spmv(mg.rep_b.p, y, mg.r2r_off.p, mg.r2r_col.p, mg.r2r_w.p, ng, false, s, mg.r2r_lane));
-  GLS_TRY(dist_allreduce_vector(c, mg.rep_b.p, ng));
-  HIP_TRY(gls::vec_set_indexed(mg.rep_b.p, r->con_dofs.p, nullptr, (int64_t)r->con_dofs.n, s));
-  if (mg.direct_ok) {  // the replica level is the coarsest: its exact solve, every rank
-    const double one = 1.0, zero = 0.0;
-    if (rocblas_set_stream(mg.blas, s) != rocblas_status_success ||
-        rocblas_dgemv(mg.blas, rocblas_operation_none, (rocblas_int)ng, (rocblas_int)ng, &one, mg.probe.p,
-                      (rocblas_int)ng, mg.rep_b.p, 1, &zero, mg.rep_x.p, 1) != rocblas_status_success)
-      return set_err(GLS_EHIP, "rocblas_dgemv failed");
-  } else {
-    GLS_TRY(gls_apply_preconditioner(r, mg.rep_b.p, mg.rep_x.p));  // the replica's own V-cycle, every rank
-  }
-  HIP_TRY(gls::vec_csr_spmv(y, mg.rep_x.p, mg.r2p_off.p, mg.r2p_col.p, mg.r2p_w.p, n, false, s, mg.r2p_lane));
-  HIP_TRY(gls::vec_set_indexed(y, c->con_dofs.p, nullptr, (int64_t)c->con_dofs.n, s));
-  HIP_TRY(gls::vec_axpy(x, 1.0, y, n, s));
-  for (int it = 0; it < post; ++it) GLS_TRY(smoother_sweep(c, x, b, y, mg.omega, zs));
-  return GLS_OK;
-}
-
-// glob (replica numbering, every rank) = the coarsest distributed level's vector loc: each rank scatters
-// its owned rows into a zeroed copy, then one sum all-reduce (RCCL: in place; callback transports
-// through their reduction buffer in chunks of 256 values)
-int replica_gather(gls_ctx *c, const double *loc, double *glob) {
-  auto &mg = c->mg;
-  gls_ctx *g = mg.lev.back();
-  auto &D = g->dist;
-  const int64_t ng = mg.replica->n_dofs, no = (int64_t)mg.rep_own_loc.n;
-  hipStream_t s = c->stream;
-  HIP_TRY(gls::vec_fill(glob, ng, 0.0, s));
-  if (no) {
-    HIP_TRY(gls::vec_pack_dofs(loc, mg.rep_own_loc.p, no, mg.rep_tmp.p, s));
-    HIP_TRY(gls::vec_unpack_dofs(glob, mg.rep_own_glob.p, no, mg.rep_tmp.p, s));
-  }
-  if (D.comm) {
-    if (D.allreduce(D.user, glob, (int)ng) != 0) return set_err(GLS_ECOMM, "replica all-reduce failed");
-    return GLS_OK;
-  }
-  for (int64_t o = 0; o < ng; o += 256) {
-    const int len = (int)std::min<int64_t>(256, ng - o);
-    HIP_TRY(hipMemcpyAsync(D.red_buf, glob + o, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
-    if (D.allreduce(D.user, D.red_buf, len) != 0) return set_err(GLS_ECOMM, "replica all-reduce failed");
-    HIP_TRY(hipMemcpyAsync(glob + o, D.red_buf, sizeof(double) * len, hipMemcpyDeviceToDevice, s));
-  }
-  return GLS_OK;
-}
-
-// x = V-cycle(b) on level l (x, b are level-l vectors)
-int mg_vcycle(gls_ctx *c, int l, const double *b, double *x) {
-  auto &mg = c->mg;
-  const int L = (int)mg.lev.size();
-  gls_ctx *g = mg.lev[l];
-  GLS_TRY(ensure_diag(g));
-  const int64_t n = g->n_dofs;
-  double *y = mgbuf(c, l, MB_Y);
-  const double *d = g->diag.p;
-  hipStream_t s = c->stream;
-  if (l == L - 1 && mg.replica) {  // the replica's cycle on the gathered right-hand side, every rank
-    GLS_TRY(replica_gather(c, b, mg.rep_b.p));
-    GLS_TRY(gls_apply_preconditioner(mg.replica, mg.rep_b.p, mg.rep_x.p));
-    HIP_TRY(gls::vec_pack_dofs(mg.rep_x.p, mg.rep_map.p, n, x, c->stream));
-    return GLS_OK;
-  }
-  if (l == L - 1 && mg.direct_ok) GLS_TRY(coarse_lu32_finish(c));
-  if (l == L - 1 && mg.direct_ok) {  // exact coarsest-level solve
-    if (mg.lu32) {  // the FP32 factor / inverse, in the matrix's order (banded: the CSR's Cuthill-McKee order)
-      const double *bb = b;
-      double *xx = x;
-      if (mg.lu_cm) {
-        HIP_TRY(gls::vec_permute(mg.lu_tmp.p, b, g->ilu.perm.p, n, 0, c->stream));
-        bb = xx = mg.lu_tmp.p;
-      }
-      if (mg.lu32_npvt) {  // x = U^-1 L^-1 b
-        const int bl = mg.lu_cm ? (int)mg.lu_bl : -1, bu = mg.lu_cm ? (int)mg.lu_bu : -1;
-        HIP_TRY(gls::vec_to_f32(bb, mg.x32.p, n, c->stream));
-        HIP_TRY(gls::dense_lu_solve_f32(mg.probe32.p, (int)n, mg.x32.p, c->stream, bl, bu));
-        if (mg.lu32_refine) {  // r = b - A x (the pinned FP64 matrix), x += LU^-1 r
-          const double one = 1.0, mone = -1.0;
-          double *r = mg.chk32.p, *x0 = mg.chk32.p + n;
-          HIP_TRY(gls::vec_from_f32(mg.x32.p, x0, n, c->stream));
-          HIP_TRY(gls::vec_copy(r, bb, n, c->stream));
-          if (rocblas_set_stream(mg.blas, c->stream) != rocblas_status_success ||
-              rocblas_dgemv(mg.blas, rocblas_operation_none, (rocblas_int)n, (rocblas_int)n, &mone, mg.probe.p,
-                            (rocblas_int)n, x0, 1, &one, r, 1) != rocblas_status_success)
-            return set_err(GLS_EHIP, "rocblas_dgemv failed");
-          HIP_TRY(gls::vec_to_f32(r, mg.x32.p, n, c->stream));
-          HIP_TRY(gls::dense_lu_solve_f32(mg.probe32.p, (int)n, mg.x32.p, c->stream, bl, bu));
-          HIP_TRY(gls::vec_from_f32(mg.x32.p, xx, n, c->stream));
-          HIP_TRY(gls::vec_axpy(xx, 1.0, x0, n, c->stream));
-        } else {
-          HIP_TRY(gls::vec_from_f32(mg.x32.p, xx, n, c->stream));
-        }
-      } else {  // x = A^-1 b
-        const float one = 1.0f, zero = 0.0f;
-        HIP_TRY(gls::vec_to_f32(bb, mg.b32.p, n, c->stream));
-        if (rocblas_set_stream(mg.blas, c->stream) != rocblas_status_success ||
-            rocblas_sgemv(mg.blas, rocblas_operation_none, (rocblas_int)n, (rocblas_int)n, &one, mg.probe32.p,
-                          (rocblas_int)n, mg.b32.p, 1, &zero, mg.x32.p, 1) != rocblas_status_success)
-          return set_err(GLS_EHIP, "rocblas_sgemv failed");
-        HIP_TRY(gls::vec_from_f32(mg.x32.p, xx, n, c->stream));
-      }
-      if (mg.lu_cm) HIP_TRY(gls::vec_permute(x, mg.lu_tmp.p, g->ilu.perm.p, n, 1, c->stream));
-      HIP_TRY(hipMemsetAsync(x + (int64_t)g->dim * g->n_vnodes, 0, sizeof(double), c->stream));  // pinned: no correction
-      return GLS_OK;
-    }
-    if (mg.lu) {
-      const double one = 1.0, zero = 0.0;
-      if (rocblas_set_stream(mg.blas, c->stream) != rocblas_status_success ||
-          rocblas_dgemv(mg.blas, rocblas_operation_none, (rocblas_int)n, (rocblas_int)n, &one, mg.probe.p,
-                        (rocblas_int)n, b, 1, &zero, x, 1) != rocblas_status_success)
-        return set_err(GLS_EHIP, "rocblas_dgemv failed");
-    } else {
-      HIP_TRY(gls::mg_dense_apply(mg.aug.p, (int)n, b, x, c->stream));
-    }
-    return GLS_OK;
-  }
-  const int pre = l == L - 1 ? mg.csweeps : mg.lpre[(size_t)l];
-  const double om = l == L - 1 ? mg.comega : mg.omega;
-  if (l == L - 1 && l > 0 && pre > 1 && coarse_graph_eligible(c, g, b, x)) {
-    GLS_TRY(ensure_diag(g));  // contents the replay reads: current for this state
-    GLS_TRY(g->smooth_f32 ? ensure_qdata32(g, !g->smooth_oseen) : ensure_qdata(g));
-    if (mg.cgraph.h && mg.cgraph_key != coarse_graph_key(g, b, x, y, pre, om)) mg.cgraph.reset();
-    if (!mg.cgraph.h) GLS_TRY(coarse_graph_capture(c, g, b, x, y, pre, om));
-    if (mg.cgraph.h) {
-      HIP_TRY(hipGraphLaunch(mg.cgraph.h, s));
-      return GLS_OK;
-    }
-  }
-  // one pre-sweep from 0 on a fused level: x = omega D^-1 b is formed inside the residual's J.v
-  const bool first_fused = pre == 1 && l < L - 1 && first_sweep_fusable(g);
-  double *zs = mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only ? mgbuf(c, l, MB_BOX) : nullptr;  // ILU smoothing scratch
-  if (pre > 0 && !first_fused && zs) {
-    GLS_TRY(ensure_ilu(g));
-    GLS_TRY(apply_ilu(g, b, x));  // first sweep from x = 0: x = M^-1 b
-    for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(g, x, b, y, om, zs));
-  } else if (pre > 0 && !first_fused) {
-    HIP_TRY(gls::mg_jacobi_update(x, b, nullptr, d, om, n, 1, s));  // first sweep from x = 0
-    for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(g, x, b, y, om));
-  } else if (pre == 0) {
-    HIP_TRY(gls::vec_fill(x, n, 0.0, s));
-  }
-  if (l == L - 1) return GLS_OK;
-  // residual -> coarse right-hand side: restrict the owned rows, export-add coarse ghost rows
-  gls_ctx *h = mg.lev[l + 1];
-  double *bc = mgbuf(c, l + 1, MB_B), *xc = mgbuf(c, l + 1, MB_X);
-  if (pre > 0 && mg_fused_restrict_ok(c, l)) {
-    // bc = R (b - A x), constrained rows zeroed: one J.v + one sum (first_fused: x = omega D^-1 b formed there too)
-    GLS_TRY(mg_residual_restrict_fused(c, l, x, b, bc, first_fused ? om : 0.0));
-  } else {
-    if (first_fused) {
-      GLS_TRY(jacobian_apply_f32(g, x, y, b, om, g->smooth_oseen));  // x = omega D^-1 b, y = b - A x
-    } else if (pre > 0) {
-      GLS_TRY(smoother_apply(g, x, y, b));  // y = b - A x
-    } else {
-      HIP_TRY(gls::vec_copy(y, b, n, s));  // x = 0: the residual is b
-    }
-    GLS_TRY(mg_restrict(c, l, y, bc));
-    HIP_TRY(gls::vec_set_indexed(bc, h->con_dofs.p, nullptr, (int64_t)h->con_dofs.n, s));
-  }
-  GLS_TRY(mg_vcycle(c, l + 1, bc, xc));
-  // prolongate the coarse correction (ghost values imported first). x += P xc in the transfer's
-  // store on one rank: the coarse correction vanishes on the coarse Dirichlet rows (zero rhs rows,
-  // D_c-scaled sweeps) and the nested Qk interpolation maps them onto the fine Dirichlet rows, so
-  // P xc is exactly 0 there, as the zeroing below makes it in the general path
-  const bool pro = mg_fused_prolong_ok(c, l);  // x += P xc inside the first post-sweep's J.v and slab sum
-  if (pro) {  // nothing here: the sweep below gathers x + P xc
-  } else if (mg_prolong_add_ok(c, l)) {
-    GLS_TRY(mg_prolong(c, l, xc, x, true));
-  } else {
-    GLS_TRY(mg_prolong(c, l, xc, y));
-    HIP_TRY(gls::vec_set_indexed(y, g->con_dofs.p, nullptr, (int64_t)g->con_dofs.n, s));
-    HIP_TRY(gls::vec_axpy(x, 1.0, y, n, s));
-  }
-  for (int it = 0; it < mg.lpost[(size_t)l]; ++it)
-    GLS_TRY(smoother_sweep(g, x, b, y, mg.omega, zs, pro && it == 0 ? xc : nullptr));
-  return GLS_OK;
-}
-
 // z = M^{-1} v : Jacobi, assembled ILU(0) or a multigrid V-cycle when attached
 int apply_prec(gls_ctx *c, const double *v, double *z) {
   if (c->mg.on && c->mg.rep_csr) return mg_vcycle_rep2(c, v, z);
@@ -2721,486 +1846,6 @@ int gls_apply_preconditioner(gls_ctx *c, const double *v, double *z) {
   return apply_prec(c, v, z);
 }
 
-int gls_mg_transfer(gls_ctx *c, int level, int direction, const double *in, double *out) {
-  GLS_TRY(check_ctx(c));
-  auto &mg = c->mg;
-  if (!mg.on) return set_err(GLS_EINVAL, "gls_mg_transfer: no multigrid attached");
-  if (level < 0 || level + 1 >= (int)mg.lev.size() || (direction != 0 && direction != 1) || !in || !out || in == out)
-    return set_err(GLS_EINVAL, "gls_mg_transfer: bad level / direction / pointers");
-  if (direction == 0) return mg_restrict(c, level, in, out);
-  double *xc = mgbuf(c, level + 1, MB_X);  // ghost import writes into the coarse vector: work on a copy
-  HIP_TRY(gls::vec_copy(xc, in, mg.lev[(size_t)level + 1]->n_dofs, c->stream));
-  return mg_prolong(c, level, xc, out);
-}
-
-int gls_mg_residual_restrict(gls_ctx *c, int level, const double *x, const double *b, double *bc, int *fused) {
-  GLS_TRY(check_ctx(c));
-  auto &mg = c->mg;
-  if (!mg.on) return set_err(GLS_EINVAL, "gls_mg_residual_restrict: no multigrid attached");
-  if (level < 0 || level + 1 >= (int)mg.lev.size() || !x || !b || !bc)
-    return set_err(GLS_EINVAL, "gls_mg_residual_restrict: bad level / pointers");
-  GLS_TRY(mg_prepare(c));  // the levels' states, as the V-cycle sees them
-  const bool f = mg_fused_restrict_ok(c, level);
-  if (fused) *fused = f ? 1 : 0;
-  if (f) return mg_residual_restrict_fused(c, level, const_cast<double *>(x), b, bc);
-  gls_ctx *g = mg.lev[(size_t)level], *h = mg.lev[(size_t)level + 1];
-  double *y = mgbuf(c, level, MB_Y);
-  GLS_TRY(smoother_apply(g, x, y, b));
-  GLS_TRY(mg_restrict(c, level, y, bc));
-  HIP_TRY(gls::vec_set_indexed(bc, h->con_dofs.p, nullptr, (int64_t)h->con_dofs.n, c->stream));
-  return GLS_OK;
-}
-
-int gls_mg_prolong_smooth(gls_ctx *c, int level, const double *xc, double *x, const double *b, double omega, int *fused) {
-  GLS_TRY(check_ctx(c));
-  auto &mg = c->mg;
-  if (!mg.on) return set_err(GLS_EINVAL, "gls_mg_prolong_smooth: no multigrid attached");
-  if (level < 0 || level + 1 >= (int)mg.lev.size() || !xc || !x || !b || x == b || omega < 0.0)
-    return set_err(GLS_EINVAL, "gls_mg_prolong_smooth: bad level / pointers / omega");
-  GLS_TRY(mg_prepare(c));  // the levels' states, as the V-cycle sees them
-  gls_ctx *g = mg.lev[(size_t)level];
-  const bool f = mg_fused_prolong_ok(c, level);
-  if (fused) *fused = f ? 1 : 0;
-  double *y = mgbuf(c, level, MB_Y);
-  double *zs = mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only ? mgbuf(c, level, MB_BOX) : nullptr;
-  double *xcw = mgbuf(c, level + 1, MB_X);  // the V-cycle's coarse vector (ghost import writes into it): a copy
-  if (xcw != xc) HIP_TRY(gls::vec_copy(xcw, xc, mg.lev[(size_t)level + 1]->n_dofs, c->stream));
-  if (f) return smoother_sweep(g, x, b, y, omega, zs, xcw);
-  if (mg_prolong_add_ok(c, level)) {
-    GLS_TRY(mg_prolong(c, level, xcw, x, true));
-  } else {
-    GLS_TRY(mg_prolong(c, level, xcw, y));
-    HIP_TRY(gls::vec_set_indexed(y, g->con_dofs.p, nullptr, (int64_t)g->con_dofs.n, c->stream));
-    HIP_TRY(gls::vec_axpy(x, 1.0, y, g->n_dofs, c->stream));
-  }
-  return smoother_sweep(g, x, b, y, omega, zs);
-}
-
-
-int gls_set_lattice(gls_ctx *c, int n1d, const int64_t *l2g) {
-  GLS_TRY(check_ctx(c));
-  if (c->dim != 3 || n1d < 2 || !l2g) return set_err(GLS_EINVAL, "gls_set_lattice: 3D, n1d >= 2, map required");
-  int lo[3] = {n1d, n1d, n1d}, hi[3] = {-1, -1, -1};
-  for (int i = 0; i < c->n_vnodes; ++i) {
-    const int64_t g = l2g[i];
-    if (g < 0 || g >= (int64_t)n1d * n1d * n1d) return set_err(GLS_EINVAL, "lattice node out of range");
-    const int x[3] = {(int)(g % n1d), (int)((g / n1d) % n1d), (int)(g / ((int64_t)n1d * n1d))};
-    for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], x[a]); hi[a] = std::max(hi[a], x[a]); }
-  }
-  int bd[3];
-  for (int a = 0; a < 3; ++a) bd[a] = hi[a] - lo[a] + 1;
-  const int64_t nbox = (int64_t)bd[0] * bd[1] * bd[2];
-  if (nbox != c->n_vnodes) return set_err(GLS_EINVAL, "local nodes do not fill a box (%lld != %d)", (long long)nbox, c->n_vnodes);
-  std::vector<int32_t> map((size_t)nbox, -1);
-  for (int i = 0; i < c->n_vnodes; ++i) {
-    const int64_t g = l2g[i];
-    const int64_t x = g % n1d - lo[0], y = (g / n1d) % n1d - lo[1], z = g / ((int64_t)n1d * n1d) - lo[2];
-    int32_t &m = map[(size_t)((z * bd[1] + y) * bd[0] + x)];
-    if (m >= 0) return set_err(GLS_EINVAL, "duplicate lattice node");
-    m = i;
-  }
-  GLS_TRY(c->lat.map.upload(map.data(), map.size()));
-  c->lat.n1d = n1d;
-  for (int a = 0; a < 3; ++a) { c->lat.box0[a] = lo[a]; c->lat.bdim[a] = bd[a]; }
-  c->lat.set = true;
-  return GLS_OK;
-}
-
-// the sweep parameters, level buffers and the coarsest-level direct solve of an attached hierarchy
-static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
-  auto &mg = c->mg;
-  mg.k = c->k;
-  mg.pre = p->pre_smooth > 0 ? p->pre_smooth : (p->pre_smooth < 0 ? 0 : 2);
-  mg.post = p->post_smooth >= 0 ? p->post_smooth : 2;
-  mg.csweeps = p->coarse_sweeps > 0 ? p->coarse_sweeps : 30;
-  mg.omega = p->omega > 0 ? p->omega : 0.6;
-  mg.comega = p->coarse_omega > 0 ? p->coarse_omega : mg.omega;
-  mg.lpre.assign((size_t)p->n_levels, mg.pre);
-  mg.lpost.assign((size_t)p->n_levels, mg.post);
-  if (p->level_sweeps)
-    for (int l = 0; l < p->n_levels; ++l) {
-      if (p->level_sweeps[2 * l] < 0 || p->level_sweeps[2 * l + 1] < 0) return set_err(GLS_EINVAL, "mg: negative level sweeps");
-      mg.lpre[(size_t)l] = p->level_sweeps[2 * l];
-      mg.lpost[(size_t)l] = p->level_sweeps[2 * l + 1];
-    }
-  for (auto *g : mg.lev) g->smooth_f32 = p->mixed_precision != 0;
-  // the smoother's operator: Newton's Jacobian, or its Oseen (Picard) part (FP32 brick levels only: the
-  // pencil J.v drops the (grad u) v terms)
-  {
-    const bool os = p->smoother_operator == 1;
-    if (p->smoother_operator < 0 || p->smoother_operator > 1) return set_err(GLS_EINVAL, "mg: smoother_operator 0 or 1");
-    for (auto *g : mg.lev) g->smooth_oseen = os && g->smooth_f32;
-  }
-  mg.ilu_smooth = p->smoother == 1 || p->smoother == 2;
-  if (p->smoother < 0 || p->smoother > 2 || (mg.ilu_smooth && !mg.csr))
-    return set_err(GLS_EINVAL, "mg: smoother 0 (Jacobi), 1 (ILU) or 2 (ILU below the finest level; gls_mg_attach_transfers hierarchies)");
-  for (int l = 0; l < p->n_levels; ++l)
-    for (int b = 0; b < MB_N; ++b) {
-      mg.bufs.emplace_back(new DevBuf<double>());
-      const bool need = b == MB_BOX ? (mg.boxed || mg.ilu_smooth) : (l > 0 || b == MB_Y);
-      if (need)
-        GLS_TRY(mg.bufs.back()->alloc(b == MB_BOX && mg.boxed ? (size_t)(4 * mg_nbox(c, l)) : (size_t)mg.lev[l]->n_dofs));
-    }
-  if (mg.ilu_smooth)  // ILU(0) on every level above the coarsest (multicolor order); smoother 2: not the finest
-    for (int l = p->smoother == 2 ? 1 : 0; l + 1 < p->n_levels; ++l) {
-      gls_ctx *g = mg.lev[(size_t)l];
-      // multicolor order on every level. As a smoother the color-by-color ILU(0) is both faster per sweep (no level-scheduled csrsv) and
-      // stronger: configs[3] --precond hmg 38 -> 26 GMRES iterations, 3.97 -> 1.37 s wall, the linear solves
-      // 1.72 -> 0.08 s (profiles/r05_app_configs3_hmg_ilu_order.txt)
-      GLS_TRY(gls_ilu_set_options(g, GLS_ILU_ORDER_MULTICOLOR, 0));
-      GLS_TRY(gls_ilu_attach(g, 0, 1e-12, 1.0));
-      mg.ilu_levels.push_back(g);  // detached again by gls_mg_detach
-    }
-  // direct coarsest solve: single GPU, coarsest level up to kDirectMax DoFs (FP64 LU up to kDirectSmall, FP32 above)
-  {
-    const int64_t nco = mg.lev.back()->n_dofs;
-    const int want = p->coarse_direct;
-    if (want > 0 && (mg.boxed || nco > kDirectMax))
-      return set_err(GLS_EINVAL, "mg: direct coarse solve needs one GPU, <= %lld DoFs", (long long)kDirectMax);
-    mg.direct = want > 0 || (want == 0 && !mg.boxed && nco <= 2048);
-    if (mg.direct) {
-      GLS_TRY(mg.probe.alloc((size_t)(nco * nco)));
-      if (nco > kDirectSmall) {
-        GLS_TRY(mg.probe32.alloc((size_t)(nco * nco)));
-        GLS_TRY(mg.b32.alloc((size_t)nco));
-        GLS_TRY(mg.x32.alloc((size_t)nco));
-      }
-      if (std::getenv("GLS_MG_COARSE_SOLVER")) GLS_TRY(mg.aug.alloc((size_t)(2 * nco * nco)));  // gj experiments
-      GLS_TRY(mg.ipiv.alloc((size_t)nco));
-      GLS_TRY(mg.info.alloc(1));
-      if (!mg.blas.h && rocblas_create_handle(&mg.blas.h) != rocblas_status_success)
-        return set_err(GLS_EHIP, "rocblas_create_handle failed");
-      rocblas_set_pointer_mode(mg.blas, rocblas_pointer_mode_host);
-      GLS_TRY(mg.unit.alloc((size_t)nco));
-      GLS_TRY(mg.status.alloc(1));
-      GLS_TRY(mg_probe_setup(c, mg.lev.back()));
-    }
-  }
-  mg.on = true;
-  mg.dirty = true;
-  // one stream for the whole V-cycle: the coarse levels' kernels are ordered with the transfers
-  for (size_t l = 1; l < mg.lev.size(); ++l)
-    if (mg.lev[l]->stream != c->stream) GLS_TRY(gls_set_stream(mg.lev[l], c->stream));
-  return GLS_OK;
-}
-
-int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
-  GLS_TRY(check_ctx(c));
-  if (!p || p->n_levels < 2 || !p->levels || p->levels[0] != c) return set_err(GLS_EINVAL, "mg: levels[0] must be ctx");
-  if (c->dim != 3 || c->k > 2 || c->k != c->kp) return set_err(GLS_EINVAL, "mg: 3D Q1-Q1 / Q2-Q2 only");
-  if (c->hang.on) return set_err(GLS_EINVAL, "mg: not with hanging-node constraints");
-  if (c->map_degree > 0) return set_err(GLS_EINVAL, "mg: nested hyper_cube levels only (not mapped cells)");
-  GLS_TRY(gls_mg_detach(c));  // a previous attach's levels / smoother ILUs
-  auto &mg = c->mg;
-  mg.boxed = c->dist.on;
-  for (int l = 0; l < p->n_levels; ++l) {
-    gls_ctx *g = p->levels[l];
-    if (!g || g->dim != 3 || g->k != c->k || g->kp != c->kp || g->dist.on != mg.boxed)
-      return set_err(GLS_EINVAL, "mg level %d: order / distribution differs from level 0", l);
-    std::array<int, 3> dm;
-    if (mg.boxed) {
-      if (!g->lat.set) return set_err(GLS_EINVAL, "mg level %d: distributed level without gls_set_lattice", l);
-      for (int a = 0; a < 3; ++a) dm[a] = g->lat.bdim[a];
-      if (l > 0) {
-        const gls_ctx *f = p->levels[l - 1];
-        if (f->lat.n1d != 2 * g->lat.n1d - 1) return set_err(GLS_EINVAL, "mg level %d not nested", l);
-        for (int a = 0; a < 3; ++a)
-          if (f->lat.box0[a] != 2 * g->lat.box0[a] || f->lat.bdim[a] != 2 * g->lat.bdim[a] - 1)
-            return set_err(GLS_EINVAL, "mg level %d: partition not nested (rank box %d)", l, a);
-      }
-    } else {
-      const int n = (int)std::lround(std::cbrt((double)g->n_vnodes));
-      if ((int64_t)n * n * n != g->n_vnodes) return set_err(GLS_EINVAL, "mg level %d is not an n^3 lattice", l);
-      if (l > 0 && mg.dims.back()[0] != 2 * n - 1) return set_err(GLS_EINVAL, "mg level %d not nested", l);
-      dm = {n, n, n};
-    }
-    mg.lev.push_back(g);
-    mg.dims.push_back(dm);
-  }
-  // 1D transfer taps: fine lattice index i sits at x = i / (2k) coarse cells from the box origin;
-  // prolongation interpolates the coarse Qk field of the parent cell (equidistant nodes, k <= 2)
-  const int K = c->k;
-  size_t xwork = 0;
-  for (int l = 0; l + 1 < p->n_levels; ++l) {
-    std::unique_ptr<gls_ctx::MG::Taps> T(new gls_ctx::MG::Taps);
-    T->two_pass = true;
-    T->q2_brick = K == 2;
-    xwork =std::max(xwork, (size_t)4 * mg.dims[l + 1][0] * mg.dims[l + 1][1] * mg.dims[l][2]);
-    for (int a = 0; a < 3; ++a) {
-      const int nf = mg.dims[l][a], nc = mg.dims[l + 1][a], ncc = (nf - 1) / (2 * K);
-      std::vector<int32_t> pi((size_t)nf * 5, 0), ri((size_t)nc * 5, 0);
-      std::vector<double> pw((size_t)nf * 5, 0.0), rw((size_t)nc * 5, 0.0);
-      std::vector<int32_t> rn((size_t)nc, 0), pn((size_t)nf, 0);
-      for (int i = 0; i < nf; ++i) {
-        const double x = (double)i / (2.0 * K);
-        const int cc = std::min((int)std::floor(x), ncc - 1);
-        const double xi = x - cc;
-        int np = 0;
-        for (int q = 0; q <= K; ++q) {
-          double L = 1.0;
-          for (int b = 0; b <= K; ++b)
-            if (b != q) L *= (xi * K - b) / (double)(q - b);
-          if (L == 0.0) continue;
-          const int j = cc * K + q;
-          pi[(size_t)i * 5 + np] = j;
-          pw[(size_t)i * 5 + np] = L;
-          ++np;
-          if (rn[(size_t)j] >= 5) return set_err(GLS_EINVAL, "mg: restriction stencil wider than 5");
-          ri[(size_t)j * 5 + rn[(size_t)j]] = i;
-          rw[(size_t)j * 5 + rn[(size_t)j]] = L;
-          ++rn[(size_t)j];
-        }
-        pn[(size_t)i] = np;
-        if (K == 2) {  // the closed form of the in-kernel restriction, checked tap by tap
-          static const double W[5][3] = {{1, 0, 0}, {0.375, 0.75, -0.125}, {0, 1, 0}, {-0.125, 0.75, 0.375}, {0, 0, 1}};
-          const int m = i - 4 * cc;
-          int nz = 0;
-          for (int q = 0; q < 3; ++q) nz += W[m][q] != 0.0;
-          bool same = np == nz;
-          for (int e = 0; same && e < np; ++e) {
-            const int q = pi[(size_t)i * 5 + e] - 2 * cc;
-            same = q >= 0 && q < 3 && pw[(size_t)i * 5 + e] == W[m][q];
-          }
-          T->q2_brick = T->q2_brick && same && nf == 2 * nc - 1;
-        }
-      }
-      if (a < 2)
-        T->two_pass = T->two_pass && gls::mg_transfer_tile_fits(0, a, nf, pi.data(), pn.data()) &&
-                      gls::mg_transfer_tile_fits(1, a, nc, ri.data(), rn.data());
-      GLS_TRY(T->pi[a].upload(pi.data(), pi.size()));
-      GLS_TRY(T->pw[a].upload(pw.data(), pw.size()));
-      GLS_TRY(T->ri[a].upload(ri.data(), ri.size()));
-      GLS_TRY(T->rw[a].upload(rw.data(), rw.size()));
-      GLS_TRY(T->pc[a].upload(pn.data(), pn.size()));
-      GLS_TRY(T->rc[a].upload(rn.data(), rn.size()));
-    }
-    mg.taps.push_back(std::move(T));
-  }
-  if (xwork) GLS_TRY(mg.xwork.alloc(xwork));
-  return mg_attach_common(c, p);
-}
-
-int gls_mg_attach_transfers(gls_ctx *c, const gls_mg_params *p, const int64_t *const *p_off, const int32_t *const *p_col,
-                            const double *const *p_w, const int64_t *const *inject) {
-  GLS_TRY(check_ctx(c));
-  if (!p || p->n_levels < 2 || !p->levels || p->levels[0] != c) return set_err(GLS_EINVAL, "mg: levels[0] must be ctx");
-  if (!p_off || !p_col || !p_w || !inject) return set_err(GLS_EINVAL, "mg: transfer arrays missing");
-
-  GLS_TRY(gls_mg_detach(c));  // a previous attach's levels / smoother ILUs
-  auto &mg = c->mg;
-  mg.csr = true;
-  for (int l = 0; l < p->n_levels; ++l) {
-    gls_ctx *g = p->levels[l];
-    // the levels may differ in degree (h-p hierarchies: the CSR transfers carry the p-level pairs of
-    // gls_fe_space_mg_transfer), not in dimension
-    if (!g || g->dim != c->dim || g->dist.on)
-      return set_err(GLS_EINVAL, "mg level %d: dimension differs from level 0, or distributed", l);
-    mg.lev.push_back(g);
-    mg.dims.push_back({0, 0, 0});
-  }
-  for (int l = 0; l + 1 < p->n_levels; ++l) {
-    const int64_t nf = mg.lev[(size_t)l]->n_dofs, nc = mg.lev[(size_t)l + 1]->n_dofs;
-    const int64_t *off = p_off[l];
-    if (!off || !p_col[l] || !p_w[l] || !inject[l] || off[0] != 0) return set_err(GLS_EINVAL, "mg transfer %d: arrays", l);
-    for (int64_t i = 0; i < nf; ++i)
-      if (off[i + 1] < off[i]) return set_err(GLS_EINVAL, "mg transfer %d: offsets not monotone", l);
-    const int64_t nnz = off[nf];
-    std::vector<int64_t> rcnt((size_t)nc + 1, 0);
-    for (int64_t j = 0; j < nnz; ++j) {
-      if (p_col[l][j] < 0 || p_col[l][j] >= nc) return set_err(GLS_EINVAL, "mg transfer %d: column out of range", l);
-      ++rcnt[(size_t)p_col[l][j] + 1];
-    }
-    for (int64_t j = 0; j < nc; ++j) rcnt[(size_t)j + 1] += rcnt[(size_t)j];
-    // R = P^T, each coarse row's terms in ascending fine row order (deterministic sums)
-    std::vector<int32_t> rcol((size_t)nnz);
-    std::vector<double> rw((size_t)nnz);
-    std::vector<int64_t> fill(rcnt.begin(), rcnt.end() - 1);
-    for (int64_t i = 0; i < nf; ++i)
-      for (int64_t j = off[i]; j < off[i + 1]; ++j) {
-        const int64_t slot = fill[(size_t)p_col[l][j]]++;
-        rcol[(size_t)slot] = (int32_t)i;
-        rw[(size_t)slot] = p_w[l][j];
-      }
-    std::vector<int32_t> inj((size_t)nc);
-    for (int64_t j = 0; j < nc; ++j) {
-      if (inject[l][j] < 0 || inject[l][j] >= nf) return set_err(GLS_EINVAL, "mg transfer %d: injection out of range", l);
-      inj[(size_t)j] = (int32_t)inject[l][j];
-    }
-    std::unique_ptr<gls_ctx::MG::Csr> X(new gls_ctx::MG::Csr);
-    X->nf = nf;
-    X->nc = nc;
-    auto lanes = [](double mean) {  // ~2 entries per lane
-      int L = 1;
-      while (L < 16 && 2.0 * L < mean) L *= 2;
-      return L;
-    };
-    X->plane = lanes((double)nnz / (double)std::max<int64_t>(nf, 1));
-    X->rlane = lanes((double)nnz / (double)std::max<int64_t>(nc, 1));
-    GLS_TRY(X->poff.upload(off, (size_t)nf + 1));
-    GLS_TRY(X->pcol.upload(p_col[l], (size_t)std::max<int64_t>(nnz, 1)));
-    GLS_TRY(X->pw.upload(p_w[l], (size_t)std::max<int64_t>(nnz, 1)));
-    GLS_TRY(X->roff.upload(rcnt.data(), rcnt.size()));
-    GLS_TRY(X->rcol.upload(rcol.data(), std::max<size_t>(rcol.size(), 1)));
-    GLS_TRY(X->rw.upload(rw.data(), std::max<size_t>(rw.size(), 1)));
-    GLS_TRY(X->inj.upload(inj.data(), inj.size()));
-    mg.xfer.push_back(std::move(X));
-  }
-  return mg_attach_common(c, p);
-}
-
-int gls_mg_set_coarse_replica(gls_ctx *c, gls_ctx *replica, int64_t n_local, const int64_t *local_to_replica) {
-  GLS_TRY(check_ctx(c));
-  auto &mg = c->mg;
-  if (!mg.on || mg.lev.size() < 2) return set_err(GLS_EINVAL, "coarse replica: attach the multigrid hierarchy first");
-  gls_ctx *g = mg.lev.back();
-  if (!replica || replica == c || replica->dist.on) return set_err(GLS_EINVAL, "coarse replica: a single-rank context");
-  if (!g->dist.on) return set_err(GLS_EINVAL, "coarse replica: the coarsest level is not distributed");
-  if (n_local != g->n_dofs || !local_to_replica) return set_err(GLS_EINVAL, "coarse replica: map of %lld rows expected",
-                                                                (long long)g->n_dofs);
-  const int64_t ng = replica->n_dofs;
-  if (ng >= INT32_MAX) return set_err(GLS_EINVAL, "coarse replica too large");
-  std::vector<int32_t> all((size_t)n_local), own_l, own_g;
-  const int64_t dv = (int64_t)g->dim * g->n_vnodes;
-  for (int64_t i = 0; i < n_local; ++i) {
-    const int64_t t = local_to_replica[i];
-    if (t < 0 || t >= ng) return set_err(GLS_EINVAL, "coarse replica: row %lld maps outside", (long long)i);
-    all[(size_t)i] = (int32_t)t;
-    const bool owned = i < dv ? i < (int64_t)g->dim * g->dist.n_owned : i - dv < g->dist.n_owned_p;
-    if (owned) {
-      own_l.push_back((int32_t)i);
-      own_g.push_back((int32_t)t);
-    }
-  }
-  GLS_TRY(mg.rep_map.upload(all.data(), all.size()));
-  GLS_TRY(mg.rep_own_loc.upload(own_l.data(), own_l.size()));
-  GLS_TRY(mg.rep_own_glob.upload(own_g.data(), own_g.size()));
-  GLS_TRY(mg.rep_b.alloc((size_t)ng));
-  GLS_TRY(mg.rep_x.alloc((size_t)ng));
-  GLS_TRY(mg.rep_tmp.alloc(std::max<size_t>(own_l.size(), 1)));
-  for (auto &u : mg.rep_u) GLS_TRY(u.alloc((size_t)ng));
-  if (replica->stream != c->stream) GLS_TRY(gls_set_stream(replica, c->stream));
-  mg.replica = replica;
-  mg.dirty = true;
-  return GLS_OK;
-}
-
-int gls_mg_attach_replica(gls_ctx *c, const gls_mg_params *p, gls_ctx *replica, const int64_t *p_off,
-                          const int32_t *p_col, const double *p_w, const int64_t *inject) {
-  GLS_TRY(check_ctx(c));
-  if (!p || !replica || replica == c || replica->dist.on || !p_off || !p_col || !p_w || !inject)
-    return set_err(GLS_EINVAL, "mg replica attach: arguments");
-  if (!c->dist.on) return set_err(GLS_EINVAL, "mg replica attach: the fine context is not distributed");
-  if (replica->dim != c->dim || replica->k != c->k || replica->kp != c->kp)
-    return set_err(GLS_EINVAL, "mg replica attach: replica order / dimension differs");
-  if (p->smoother < 0 || p->smoother > 1) return set_err(GLS_EINVAL, "mg replica attach: smoother 0 or 1");
-  GLS_TRY(gls_mg_detach(c));
-  auto &mg = c->mg;
-  const int64_t n = c->n_dofs, ng = replica->n_dofs;
-  if (ng >= INT32_MAX) return set_err(GLS_EINVAL, "mg replica attach: replica too large");
-  const int64_t dv = (int64_t)c->dim * c->n_vnodes;
-  auto owned = [&](int64_t i) { return i < dv ? i < (int64_t)c->dim * c->dist.n_owned : i - dv < c->dist.n_owned_p; };
-  // P on the local rows; R = the owned rows' P^T (rows = replica DoFs, local fine columns in ascending order)
-  const int64_t nnz = p_off[n];
-  std::vector<int64_t> roff((size_t)ng + 1, 0);
-  for (int64_t i = 0; i < n; ++i) {
-    if (p_off[i + 1] < p_off[i]) return set_err(GLS_EINVAL, "mg replica attach: P offsets");
-    for (int64_t e = p_off[i]; e < p_off[i + 1]; ++e) {
-      if (p_col[e] < 0 || p_col[e] >= ng) return set_err(GLS_EINVAL, "mg replica attach: P column %d", p_col[e]);
-      if (owned(i)) ++roff[(size_t)p_col[e] + 1];
-    }
-  }
-  for (int64_t r = 0; r < ng; ++r) roff[(size_t)r + 1] += roff[(size_t)r];
-  std::vector<int32_t> rcol((size_t)roff[(size_t)ng]);
-  std::vector<double> rw(rcol.size());
-  std::vector<int64_t> fill(roff.begin(), roff.end() - 1);
-  for (int64_t i = 0; i < n; ++i)
-    if (owned(i))
-      for (int64_t e = p_off[i]; e < p_off[i + 1]; ++e) {
-        const int64_t at = fill[(size_t)p_col[e]]++;
-        rcol[(size_t)at] = (int32_t)i;
-        rw[(size_t)at] = p_w[e];
-      }
-  std::vector<int32_t> ic, iff;
-  for (int64_t r = 0; r < ng; ++r)
-    if (inject[r] >= 0) {
-      if (inject[r] >= n || !owned(inject[r])) return set_err(GLS_EINVAL, "mg replica attach: inject[%lld] not owned", (long long)r);
-      ic.push_back((int32_t)r);
-      iff.push_back((int32_t)inject[r]);
-    }
-  GLS_TRY(mg.r2p_off.upload(p_off, (size_t)n + 1));
-  GLS_TRY(mg.r2p_col.upload(p_col, std::max<size_t>((size_t)nnz, 1)));
-  GLS_TRY(mg.r2p_w.upload(p_w, std::max<size_t>((size_t)nnz, 1)));
-  GLS_TRY(mg.r2r_off.upload(roff.data(), roff.size()));
-  if (rcol.empty()) {
-    rcol.push_back(0);
-    rw.push_back(0.0);
-  }
-  GLS_TRY(mg.r2r_col.upload(rcol.data(), rcol.size()));
-  GLS_TRY(mg.r2r_w.upload(rw.data(), rw.size()));
-  auto lanes = [](double mean) { return mean > 24 ? 16 : mean > 6 ? 4 : 1; };
-  mg.r2p_lane = lanes(n ? (double)nnz / (double)n : 0.0);
-  mg.r2r_lane = lanes(ng ? (double)(roff[(size_t)ng]) / (double)ng : 0.0);
-  if (ic.empty()) {
-    ic.push_back(0);
-    iff.push_back(0);
-  }
-  GLS_TRY(mg.r2inj_c.upload(ic.data(), ic.size()));
-  GLS_TRY(mg.r2inj_f.upload(iff.data(), iff.size()));
-  if (ic.size() == 1 && inject[ic[0]] < 0) mg.r2inj_c.n = mg.r2inj_f.n = 0;  // no owned source on this rank
-  GLS_TRY(mg.rep_b.alloc((size_t)ng));
-  GLS_TRY(mg.rep_x.alloc((size_t)ng));
-  GLS_TRY(mg.rep_tmp.alloc(std::max<size_t>(ic.size(), 1)));
-  for (auto &u : mg.rep_u) GLS_TRY(u.alloc((size_t)ng));
-  // smoothing on the distributed fine level: damped Jacobi or ILU(0) (per-rank blocks, Ifpack overlap 0)
-  mg.lev.assign(1, c);
-  mg.pre = p->pre_smooth > 0 ? p->pre_smooth : (p->pre_smooth < 0 ? 0 : 2);
-  mg.post = p->post_smooth >= 0 ? p->post_smooth : 2;
-  mg.lpre.assign(1, mg.pre);
-  mg.lpost.assign(1, mg.post);
-  mg.omega = p->omega > 0 ? p->omega : 0.6;
-  mg.comega = mg.omega;
-  mg.ilu_smooth = p->smoother == 1;
-  for (int b = 0; b < MB_N; ++b) {
-    mg.bufs.emplace_back(new DevBuf<double>());
-    if (b == MB_Y || (b == MB_BOX && mg.ilu_smooth)) GLS_TRY(mg.bufs.back()->alloc((size_t)n));
-  }
-  if (mg.ilu_smooth) {
-    GLS_TRY(gls_ilu_set_options(c, GLS_ILU_ORDER_MULTICOLOR, 0));
-    GLS_TRY(gls_ilu_attach(c, 0, 1e-12, 1.0));
-    mg.ilu_levels.push_back(c);
-  }
-  // a replica without a hierarchy of its own is the coarsest level: exact LU when asked (coarse_direct > 0)
-  if (p->coarse_direct > 0 && !replica->mg.on) {
-    if (ng > 8192) return set_err(GLS_EINVAL, "mg replica attach: direct coarse solve needs <= 8192 DoFs");
-    mg.direct = true;
-    GLS_TRY(mg.probe.alloc((size_t)(ng * ng)));
-    GLS_TRY(mg.ipiv.alloc((size_t)ng));
-    GLS_TRY(mg.info.alloc(1));
-    if (!mg.blas.h && rocblas_create_handle(&mg.blas.h) != rocblas_status_success)
-      return set_err(GLS_EHIP, "rocblas_create_handle failed");
-    rocblas_set_pointer_mode(mg.blas, rocblas_pointer_mode_host);
-    GLS_TRY(mg.unit.alloc((size_t)ng));
-    GLS_TRY(mg.status.alloc(1));
-    GLS_TRY(mg_probe_setup(c, replica));
-  }
-  if (replica->stream != c->stream) GLS_TRY(gls_set_stream(replica, c->stream));
-  mg.rep2 = replica;
-  mg.rep_csr = true;
-  mg.on = true;
-  mg.dirty = true;
-  return GLS_OK;
-}
-
-int gls_mg_detach(gls_ctx *c) {
-  GLS_TRY(check_ctx(c));
-  for (auto *g : c->mg.lev) g->smooth_f32 = g->smooth_oseen = false;
-  // the ILU(0) smoothers the attach put on the levels (level 0 is this context) go with the multigrid, so
-  // the preconditioner falls back to Jacobi (gls_native.h) and not to a leftover smoother ILU
-  for (auto *g : c->mg.ilu_levels) GLS_TRY(gls_ilu_detach(g));
-  c->mg.side.reset();  // (a coarse factorization in flight reads the buffers the assignment frees)
-  c->mg = gls_ctx::MG();
-  return GLS_OK;
-}
 
 // --------------------------------------------------------------------------------------------
 // GMRES(m), right preconditioned (Jacobi, the V-cycle or the assembled ILU). Orthogonalisation:

@@ -1,6 +1,7 @@
 // gls_ctx.hpp -- internal header of the library's host side (not installed, not part of include/): the context
-// struct behind the C-ABI's opaque gls_ctx, the device buffer and error macros every host translation unit uses,
-// and the helpers that more than one of them needs (namespace gls_impl; each is defined in the file named).
+// struct behind the C-ABI's opaque gls_ctx, the device buffer and error macros every host translation unit uses
+// (gls_devbuf.hpp), and the helpers that more than one of them needs (namespace gls_impl; each is defined in the
+// file named).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,35 +9,18 @@
 #include <cstdint>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include <rocblas/rocblas.h>
-#include <rocsolver/rocsolver.h>
 #include <rocsparse/rocsparse.h>
 #include <rccl/rccl.h>
 
 #include "../../include/gls_native.h"
 #include "gls_common.hpp"
+#include "gls_devbuf.hpp"
 #include "gls_error.hpp"
 #include "gls_launch.hpp"
-
-namespace gls_impl {
-// sets the thread-local last-error string (gls_last_error) and returns code (gls_api.cpp)
-int set_err(int code, const char *fmt, ...);
-}  // namespace gls_impl
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return ::gls_impl::set_err(GLS_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-#define GLS_TRY(expr)          \
-  do {                         \
-    int r_ = (expr);           \
-    if (r_ < 0) return r_;     \
-  } while (0)
+#include "gls_mg_coarse.hpp"
 
 #define RS_TRY(x)                                                                        \
   do {                                                                                   \
@@ -44,45 +28,6 @@ int set_err(int code, const char *fmt, ...);
     if (rs_ != rocsparse_status_success) return ::gls_impl::set_err(GLS_EHIP, "%s: rocsparse status %d", #x, (int)rs_); \
   } while (0)
 
-namespace gls_impl {
-
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
-  DevBuf &operator=(DevBuf &&o) noexcept {
-    if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  int alloc(size_t count) {
-    release();
-    if (count == 0) return GLS_OK;
-    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) {
-      p = nullptr;
-      return set_err(GLS_ENOMEM, "hipMalloc of %zu bytes failed", count * sizeof(T));
-    }
-    n = count;
-    return GLS_OK;
-  }
-  int upload(const T *h, size_t count) {
-    GLS_TRY(alloc(count));
-    if (count && hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_err(GLS_EHIP, "upload failed");
-    return GLS_OK;
-  }
-};
-
-}  // namespace gls_impl
 using gls_impl::DevBuf;
 
 struct gls_ctx {
@@ -327,107 +272,13 @@ struct gls_ctx {
     std::vector<std::unique_ptr<Csr>> xfer;
     std::vector<gls_ctx *> ilu_levels;  // levels whose ILU(0) smoother this attach created (smoother = 1)
     DevBuf<double> xwork;  // two-pass transfer intermediate (coarse xy x fine z, 4 fields)
-    // coarsest level: direct solve with the probed, regularised, inverted Jacobian
-    bool direct = false, direct_ok = false;
+    // coarsest level: direct solve with the probed, regularised, factored Jacobian (gls_mg_coarse.hpp; coarse.ok:
+    // this state's factorization stands)
+    bool direct = false;
     // per-cell coarsest level: its matrix for the direct solve assembled by the ILU's colored batched probes
     // (a structure-only ILU(0) on that level, never factored) instead of one J.v per column
     gls_ctx *probe_ilu = nullptr;
-    DevBuf<int32_t> pinv;
-    // direct solve by LU (rocSOLVER getrf + getri -> explicit inverse, applied by rocBLAS gemv) with
-    // the first pressure DoF pinned (enclosed-flow gauge); falls back to the one-workgroup
-    // Gauss-Jordan (mg_dense_invert) for small levels or when the LU reports a zero pivot
-    bool lu = false;
-    // large coarsest levels (kDirectSmall < n <= kDirectMax, e.g. a Q1-Q1 p-level of a 4.7 k-cell base mesh):
-    // the pinned FP64 matrix rounded to FP32, pivoted sgetrf + sgetri, applied by sgemv (a preconditioner's
-    // coarse solve: FP32 rounding of A^-1 is far below the V-cycle's own error; half the bytes and the FP32
-    // matrix-core rate for the O(n^3) setup)
-    bool lu32 = false;
-    bool lu32_npvt = false;  // the FP32 factor is unpivoted (applied by dense_lu_solve_f32), else an explicit inverse
-    bool lu32_refine = false;  // ... applied with one step of iterative refinement against the FP64 matrix
-    // banded coarse matrix: the probed CSR's Cuthill-McKee order kept (the dense array holds A in that order), its
-    // lower / upper bandwidths; the factorization works by column blocks as wide as the band (no fill outside it
-    // without pivoting) and the solves skip the blocks outside it. configs[4]'s 25 k-DoF Q1-Q1 p-level: ~1.9 k
-    bool lu_cm = false;
-    int64_t lu_bl = -1, lu_bu = -1, lu_pin_cm = -1;
-    DevBuf<int32_t> lu_ident;  // identity permutation (csr_to_dense in the CSR's own order)
-    DevBuf<double> lu_tmp;     // the coarse right-hand side / correction in that order
-    DevBuf<float> probe32, b32, x32;
-    DevBuf<double> chk32;    // the FP32 factor's check: A x - b for b = 1 (FP64)
-    int64_t npvt_ipiv_n = -1;  // ipiv holds the identity permutation of this size (unpivoted LU)
-    struct Blas {  // owning rocBLAS handle (movable, destroyed with the MG state)
-      rocblas_handle h = nullptr;
-      Blas() = default;
-      Blas(const Blas &) = delete;
-      Blas &operator=(const Blas &) = delete;
-      Blas(Blas &&o) noexcept : h(o.h) { o.h = nullptr; }
-      Blas &operator=(Blas &&o) noexcept {
-        if (this != &o) {
-          if (h) rocblas_destroy_handle(h);
-          h = o.h;
-          o.h = nullptr;
-        }
-        return *this;
-      }
-      ~Blas() {
-        if (h) rocblas_destroy_handle(h);
-      }
-      operator rocblas_handle() const { return h; }
-    } blas;
-    DevBuf<int> ipiv, info;
-    DevBuf<double> probe, aug, unit;
-    DevBuf<double> probe_bak;  // the probed coarse matrix kept for the pivoted retry of an unpivoted LU
-    DevBuf<double> chk;        // coarse_inverse_check's y = A^-1 e and z = A y
-    DevBuf<int> status;
-    // the FP32 unpivoted factorization and its check run on a stream of their own, overlapping the finer levels'
-    // ILU setup and first smoothing on the context stream; the first coarse solve waits for them
-    // (coarse_lu32_finish). Declared after the buffers it uses, so it is destroyed (synchronized) first.
-    // rocSOLVER's getrf returns to the host only when the factorization is done (82-89 ms of host time at
-    // n = 25000, box r06v), so the calls are made from a worker thread: the host thread queues the finer levels'
-    // setup meanwhile
-    struct Side {
-      hipStream_t s = nullptr;
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      std::thread worker;
-      int rc = 0;  // the worker's result: 0, or the failing call's number
-      Side() = default;
-      Side(const Side &) = delete;
-      Side &operator=(const Side &) = delete;
-      Side(Side &&o) noexcept : s(o.s), e0(o.e0), e1(o.e1), worker(std::move(o.worker)), rc(o.rc) {
-        o.s = nullptr, o.e0 = o.e1 = nullptr;
-      }
-      Side &operator=(Side &&o) noexcept {
-        if (this != &o) {
-          reset();
-          s = o.s, e0 = o.e0, e1 = o.e1, worker = std::move(o.worker), rc = o.rc;
-          o.s = nullptr, o.e0 = o.e1 = nullptr;
-        }
-        return *this;
-      }
-      void join() {
-        if (worker.joinable()) worker.join();
-      }
-      hipError_t ensure() {
-        if (s) return hipSuccess;
-        hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&e0, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&e1, hipEventDisableTiming);
-        return e;
-      }
-      void reset() {
-        join();
-        if (s) {
-          (void)hipStreamSynchronize(s);
-          (void)hipStreamDestroy(s);
-        }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        s = nullptr, e0 = e1 = nullptr;
-      }
-      ~Side() { reset(); }
-    } side;
-    bool lu_pending = false;  // side-stream factorization in flight, not yet checked
-    int64_t lu_n = 0, lu_pin = 0;
-    DevBuf<double> lu_rel;  // |A x - 1| of the check (device pointer mode)
+    gls_impl::CoarseSolve coarse;
     // coarsest-level Jacobi sweeps (single rank, fused brick path) replayed as one HIP graph: the
     // ~2×csweeps tiny launches per V-cycle are captured once per state (mg_prepare) and launched
     // as a single graph by every V-cycle of that Newton step
@@ -558,6 +409,38 @@ inline size_t cell_cache_size(const gls_ctx *c) {
   const int dim = c->dim;
   return (size_t)c->n_cells * (size_t)gls::ipow(c->nq1d, dim) * (size_t)(dim + dim * dim + 1 + dim);
 }
+
+// brick launch output: the slab (allocated on first use) or nullptr (atomics into a zeroed y)
+double *brick_slab(gls_ctx *c);
+// distributed hooks (no-ops on a single rank): ghost values imported into x; ghost rows' sums export-added into y;
+// in-place sum over ranks of a device vector
+int dist_import(gls_ctx *c, double *x);
+int dist_export_add(gls_ctx *c, double *y);
+int dist_allreduce_vector(gls_ctx *c, double *v, int64_t n);
+// the brick J.v's linearization at the quadrature points, once per state; its FP32 copy (full = false: u and tau
+// suffice, the Oseen smoother operator)
+int ensure_qdata(gls_ctx *c);
+int ensure_qdata32(gls_ctx *g, bool full = true);
+// FP32 kernels write their brick-surface partial sums in FP32
+bool slab_f32();
+// the V-cycle's operator and sweeps on level g (mixed precision and the Oseen operator per gls_mg_params):
+// y = A v, or y = rb - A v; first_omega > 0 (only where first_sweep_fusable): v formed as the first damped-Jacobi
+// sweep from 0 inside the J.v
+bool first_sweep_fusable(gls_ctx *g);
+int jacobian_apply_f32(gls_ctx *g, const double *v, double *y, const double *rb = nullptr, double first_omega = 0.0,
+                       bool oseen = false);
+int smoother_apply(gls_ctx *g, const double *v, double *y, const double *rb = nullptr);
+// one smoothing sweep on x: damped Jacobi, or the level's ILU(0) when z (scratch) is given and it is attached;
+// pxc != nullptr (only where the prolongation fuses): the sweep starts from x + P pxc
+int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double omega, double *z = nullptr,
+                   const double *pxc = nullptr);
+
+// ---- gls_mg.cpp: the geometric multigrid. mg_prepare re-discretises the levels at the Jacobian's state and factors
+// the coarsest one (no-op unless the state changed); x = V-cycle(b) on level l, and with the replica hierarchy below
+// a distributed fine level (gls_mg_attach_replica)
+int mg_prepare(gls_ctx *c);
+int mg_vcycle(gls_ctx *c, int l, const double *b, double *x);
+int mg_vcycle_rep2(gls_ctx *c, const double *b, double *x);
 
 // ---- gls_ilu.cpp: the assembled ILU (probe the operator into the CSR values; probe + perturb + factor once per
 // Jacobian state; z = P^T U^-1 L^-1 P v)

@@ -1,6 +1,6 @@
 // gls_ilu.cpp -- the device side of the assembled ILU(k) preconditioner: attach (download, the host-only plan of
 // gls_ilu_plan.cpp, across ranks the collective column-tag exchange, uploads, rocSPARSE analysis), probing,
-// factorization and the triangular solves. The multigrid's ILU smoother (gls_api.cpp) calls ensure_ilu / apply_ilu.
+// factorization and the triangular solves. The multigrid's ILU smoother (gls_api.cpp, gls_mg.cpp) calls ensure_ilu / apply_ilu.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>

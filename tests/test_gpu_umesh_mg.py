@@ -72,31 +72,48 @@ def test_umesh_multigrid_linear_solve(name, dim, spec, flat, k, kp, smoother):
     assert its_mg * 2 < its_j, (its_mg, its_j)
 
 
+_large = []
+
+
+def _large_shell_levels():
+    """the Q2-Q1 cylinder shell at refinement 3 above its refinement-2 level (30816 DoFs, the FP32 coarse LU's
+    range), built once: (level problems, their transfer, the fine state)"""
+    if not _large:
+        from softx_2020_200_amd.native import UMesh
+        m = UMesh(3, "cylinder_shell", "1 : 0.25 : 1 : 8 : 2")
+        m.refine_global(3)
+        hf = m.fe_space_handle(2, 1, qmapping_all=True)
+        hc = m.coarsen_to(2).fe_space_handle(2, 1, qmapping_all=True)
+        probs = [mapped_level(h.data, 1.0) for h in (hf, hc)]
+        assert 8192 < probs[1].n_dofs <= 40000, probs[1].n_dofs
+        Xv = hf.data["vnode_x"]
+        u = np.concatenate([np.stack([-Xv[:, 1], Xv[:, 0], 0.3 * np.sin(3 * Xv[:, 2])], 1).reshape(-1),
+                            np.cos(hf.data["pnode_x"][:, 0])])
+        probs[0].apply_nonzero_constraints(u)
+        _large.append((probs, hf.mg_transfer_from(hc), u))
+    return _large[0]
+
+
+def _large_shell_attached():
+    """fresh contexts of those levels with the V-cycle attached (ILU smoothing, direct coarse solve) at the state"""
+    probs, xfer, u = _large_shell_levels()
+    ctxs = [context_for(q) for q in probs]
+    ctxs[0].attach_multigrid_transfers(ctxs[1:], [xfer], pre_smooth=1, post_smooth=1, omega=0.6,
+                                       coarse_direct=1, smoother="ilu")
+    U = cuda(u)
+    ctxs[0].apply_dirichlet(U)
+    ctxs[0].set_state(U, cuda(np.zeros(probs[0].n_dofs)))
+    return probs, ctxs, U
+
+
 @pytest.mark.gpu
 def test_large_coarsest_level_fp32_lu(monkeypatch, capfd):
     """a coarsest level above 8192 DoFs (the Q2-Q1 cylinder shell at refinement 2, 30816 DoFs, under its
     refinement-3 level): the FP32 unpivoted LU factored by the worker thread on the side stream, its check
     |A x - 1| / |1| taken (no pivoted fallback; the matrix kept banded in the probe CSR's Cuthill-McKee order), and
     the V-cycle-preconditioned GMRES converging"""
-    from softx_2020_200_amd.native import UMesh
-    m = UMesh(3, "cylinder_shell", "1 : 0.25 : 1 : 8 : 2")
-    m.refine_global(3)
-    hf = m.fe_space_handle(2, 1, qmapping_all=True)
-    hc = m.coarsen_to(2).fe_space_handle(2, 1, qmapping_all=True)
-    probs = [mapped_level(h.data, 1.0) for h in (hf, hc)]
-    assert 8192 < probs[1].n_dofs <= 40000, probs[1].n_dofs
-    p = probs[0]
-    Xv = hf.data["vnode_x"]
-    u = np.concatenate([np.stack([-Xv[:, 1], Xv[:, 0], 0.3 * np.sin(3 * Xv[:, 2])], 1).reshape(-1),
-                        np.cos(hf.data["pnode_x"][:, 0])])
-    p.apply_nonzero_constraints(u)
-    ctxs = [context_for(q) for q in probs]
     monkeypatch.setenv("GLS_MG_VERBOSE", "1")
-    ctxs[0].attach_multigrid_transfers(ctxs[1:], [hf.mg_transfer_from(hc)], pre_smooth=1, post_smooth=1, omega=0.6,
-                                       coarse_direct=1, smoother="ilu")
-    U = cuda(u)
-    ctxs[0].apply_dirichlet(U)
-    ctxs[0].set_state(U, cuda(np.zeros(p.n_dofs)))
+    probs, ctxs, U = _large_shell_attached()
     rhs = ctxs[0].residual()
     x, its, res, ok = ctxs[0].solve_linear(rhs, ctxs[0].zeros(), max_iterations=200, restart=50,
                                            relative_residual=1e-8, minimum_residual=1e-300, true_residual=True)
@@ -115,3 +132,24 @@ def test_large_coarsest_level_fp32_lu(monkeypatch, capfd):
     assert all(r == (c >= 1e-2) for r, c in zip(refined, checks)), lines
     assert "pivoted LU + inverse" not in log, log[-2000:]
     assert its <= 40, its
+
+
+@pytest.mark.gpu
+def test_destroy_with_coarse_factorization_in_flight():
+    """the same hierarchy prepared (gls_mg_residual_restrict prepares the levels and queues the FP32 coarse
+    factorization on its worker thread and side stream, without the coarse solve that waits for it) and its contexts
+    destroyed at once, no V-cycle and no detach: the worker is joined before the buffers it writes are freed, and
+    the process goes on to a fresh small context with a finite residual"""
+    import torch
+    probs, ctxs, U = _large_shell_attached()
+    x = torch.zeros(probs[0].n_dofs, dtype=torch.float64, device="cuda")
+    ctxs[0].mg_residual_restrict(0, x, x.clone(), torch.zeros(probs[1].n_dofs, dtype=torch.float64, device="cuda"))
+    for c in ctxs:
+        c.close()
+    m = make_mesh(3, [c for c in CASES if c[0] == "rect3d"][0][2])
+    q = mapped_level(m.fe_space_handle(1, 1, qmapping_all=True).data, 0.1)
+    small = context_for(q)
+    small.set_state(cuda(np.zeros(q.n_dofs)), cuda(np.zeros(q.n_dofs)))
+    r = small.residual()
+    torch.cuda.synchronize()
+    assert r.numel() == q.n_dofs and bool(torch.isfinite(r).all())
