@@ -997,12 +997,13 @@ int multidot_async(gls_ctx *c, const double *A, int64_t lda, int nk, const doubl
   return err;
 }
 int multiaxpy_dots_async(gls_ctx *c, double *w, const double *V, int64_t lda, int nk, const double *h, bool dots,
-                         double *out, double *hp, const double **dev_res, double scale = 1.0) {
+                         double *out, double *hp, const double **dev_res, double scale = 1.0, double *x0 = nullptr,
+                         const double *x0d = nullptr, double x0omega = 0.0) {
   const int64_t n1 = c->dist.on ? (int64_t)c->dim * c->dist.n_owned : c->n_dofs;
   const int64_t off2 = c->dist.on ? (int64_t)c->dim * c->n_vnodes : 0;
   const int64_t n2 = c->dist.on ? c->dist.n_owned_p : 0;
   HIP_TRY(gls::vec_multiaxpy_dots(w, V, lda, nk, h, 1.0, c->n_dofs, n1, off2, n2, dots, scale, out, c->work.p,
-                                  c->stream));
+                                  c->stream, x0, x0d, x0omega));
   int err;
   *dev_res = reduce_dots_async(c, out, dots ? nk + 1 : 1, hp, &err);
   return err;
@@ -1248,6 +1249,7 @@ int gls_set_time(gls_ctx *c, int scheme, const double ts[4]) {
 int gls_set_state(gls_ctx *c, const double *u, const double *u1, const double *u2, const double *u3) {
   GLS_TRY(check_ctx(c));
   if (!u) return set_err(GLS_EINVAL, "u is null");
+  c->bnorm2_of = nullptr;
   c->u = u;
   c->u1 = u1;
   c->u2 = u2;
@@ -1405,6 +1407,7 @@ int gls_dist_attach_dofs(gls_ctx *c, int64_t n_owned_vnodes, int64_t n_owned_pno
 int gls_residual(gls_ctx *c, double *rhs) {
   GLS_TRY(check_ctx(c));
   if (!rhs) return set_err(GLS_EINVAL, "rhs is null");
+  c->bnorm2_of = nullptr;
   GLS_TRY(run_cell(c, gls::MODE_RESIDUAL, nullptr, rhs));
   HIP_TRY(gls::vec_set_indexed(rhs, c->con_dofs.p, nullptr, (int64_t)c->con_dofs.n, c->stream));
   return GLS_OK;
@@ -1419,6 +1422,7 @@ int gls_residual(gls_ctx *c, double *rhs) {
 int gls_residual_and_diagonal(gls_ctx *c, double *rhs, double *d) {
   GLS_TRY(check_ctx(c));
   if (!rhs) return set_err(GLS_EINVAL, "rhs is null");
+  c->bnorm2_of = nullptr;
   if (!c->u) return set_err(GLS_EINVAL, "gls_set_state was not called");
   if (c->n_hist > 0 && !c->u1) return set_err(GLS_EINVAL, "scheme needs solution_m1");
   if (c->n_hist > 1 && !c->u2) return set_err(GLS_EINVAL, "scheme needs solution_m2");
@@ -1827,10 +1831,11 @@ int gls_set_hanging(gls_ctx *c, int64_t n, const int64_t *dofs, const int64_t *o
 }
 
 namespace {
-// z = M^{-1} v : Jacobi, assembled ILU(0) or a multigrid V-cycle when attached
-int apply_prec(gls_ctx *c, const double *v, double *z) {
+// z = M^{-1} v : Jacobi, assembled ILU(0) or a multigrid V-cycle when attached. x0_ready (only where
+// mg_fine_first_producer allows): z already holds the V-cycle's first sweep from 0 on v
+int apply_prec(gls_ctx *c, const double *v, double *z, bool x0_ready = false) {
   if (c->mg.on && c->mg.rep_csr) return mg_vcycle_rep2(c, v, z);
-  if (c->mg.on) return mg_vcycle(c, 0, v, z);
+  if (c->mg.on) return mg_vcycle(c, 0, v, z, x0_ready);
   if (c->ilu.on && !c->ilu.probe_only) return apply_ilu(c, v, z);
   HIP_TRY(gls::vec_div(z, v, c->diag.p, c->n_dofs, c->stream));
   return GLS_OK;
@@ -1941,6 +1946,8 @@ static int solve_bicgstab(gls_ctx *c, const double *b, double *x, gls_linear_par
 int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *prm) {
   GLS_TRY(check_ctx(c));
   if (!b || !x || !prm) return set_err(GLS_EINVAL, "null argument");
+  const double *const bnorm2_of = c->bnorm2_of;  // consumed by this solve, whichever way it ends
+  c->bnorm2_of = nullptr;
   const int m = prm->restart > 0 ? std::min(prm->restart, 200) : 30;
   const int64_t n = c->n_dofs;
   if (c->krylov_m != m || !c->krylov.p) {
@@ -1972,8 +1979,9 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
   if (keepz && c->zbasis.n != (size_t)m * n) GLS_TRY(c->zbasis.alloc((size_t)m * n));
   double *V = c->krylov.p, *z = c->tmp1.p, *r = c->tmp2.p;
   hipStream_t s = c->stream;
-  double bnorm2;
-  GLS_TRY(device_dot(c, b, b, &bnorm2));
+  // ||b||^2: Newton's, when it just formed it from this vector with the same reduction (bitwise the dot below)
+  double bnorm2 = c->bnorm2_val;
+  if (bnorm2_of != b || std::getenv("GLS_GMRES_NO_NORM_REUSE") != nullptr) GLS_TRY(device_dot(c, b, b, &bnorm2));
   const double tol = std::max(prm->relative_residual * std::sqrt(bnorm2), prm->minimum_residual);
   // x = 0: with the Z basis the first update writes x = Z y without reading it (x_zero), and the first
   // restart cycle starts from r = b itself (no copy)
@@ -1991,6 +1999,17 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
   // GLS_GMRES_REPAIR_MEASURED=1 (the repair pass always normalises by the measured norm)
   const double repair_tol = std::getenv("GLS_GMRES_REPAIR_TOL") ? std::atof(std::getenv("GLS_GMRES_REPAIR_TOL")) : 1e-8;
   const bool repair_measured = std::getenv("GLS_GMRES_REPAIR_MEASURED") != nullptr;
+  // GLS_GMRES_FULL_LAST_COLUMN=1 (read per call): project (and repair) the column at which the solve converges
+  // too, although nothing reads v_{j+1} then (A/B runs and tests)
+  const char *fle = std::getenv("GLS_GMRES_FULL_LAST_COLUMN");
+  const bool full_last = fle && std::atoi(fle) != 0;
+  std::vector<double> hcol((size_t)m + 2);
+  // the projection that writes v_{j+1} also stores the next V-cycle's first sweep from 0 into its x, Z's slot
+  // j + 1 (x0d: the fine level's diagonal; nullptr: the cycle launches the update itself)
+  const double *x0d = nullptr;
+  double x0omega = 0.;
+  if (keepz) GLS_TRY(mg_fine_first_producer(c, &x0d, &x0omega));
+  bool x0_ready = false;  // Z's slot j holds that sweep for column j
   std::vector<double> Gm((size_t)(m + 1) * (m + 1), 0.0);
   bool converged = beta <= tol;
   const bool lverbose = std::getenv("GLS_ILU_VERBOSE") != nullptr;
@@ -2002,10 +2021,13 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
     g[0] = beta;
     int j = 0;
     double res = beta;
+    x0_ready = false;
     for (; j < m && it < prm->max_iterations; ++j) {
       double *vj = V + (int64_t)j * n, *w = V + (int64_t)(j + 1) * n;
       double *zj = keepz ? c->zbasis.p + (int64_t)j * n : z;
-      GLS_TRY(apply_prec(c, vj, zj));
+      GLS_TRY(apply_prec(c, vj, zj, x0_ready));
+      x0_ready = false;
+      double *x0 = x0d && j + 1 < m && j + 1 <= 8 ? c->zbasis.p + (int64_t)(j + 1) * n : nullptr;
       GLS_TRY(gls_jacobian_apply(c, zj, w));
       // h = V[0..j]^T w and ||w||^2 in one pass. The Gram-Schmidt passes are chained on the stream:
       // each projection reads the previous pass's dots from device memory (scal / scal2 alternate),
@@ -2017,6 +2039,7 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
       double wn2, wnorm, wnorm0;
       bool normalized = false;  // w already scaled to v_{j+1} (H(j+1, j) set) by the fused DGKS pass
       bool done = false;        // the Gram-corrected single projection below handled this column
+      bool rotated = false;     // the column converged before its projection: H, cs, sn, g already rotated
       if (gram) {
         // Gram-corrected classical Gram-Schmidt: ONE projection pass with h = (2I - G) h1, where
         // h1 = V^T w and G = V^T V (unit diagonal, off-diagonal part Gm measured by the previous
@@ -2040,11 +2063,43 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
         for (int i = 0; i <= j; ++i) q += hc[i] * hc[i] - 2.0 * hc[i] * hp1[i];
         for (int i = 0; i <= j; ++i)
           for (int k = i + 1; k <= j; ++k) q += 2.0 * hc[i] * hc[k] * G(i, k);
-        if (q > 1e-20 * wn0sq && q > 0.) {
-          const double est = std::sqrt(q);
+        const bool qok = q > 1e-20 * wn0sq && q > 0.;
+        const double est = qok ? std::sqrt(q) : 0.;
+        // hc and est are this column of H before any repair: rotate a copy and form the residual estimate before
+        // the projection is launched. On the column at which the solve converges nothing reads v_{j+1} (the update
+        // x += Z y follows), so its projection, its repair pass and its Gram column are skipped and the rotated
+        // copy is committed here (rotated: the Givens code below does not run again for this column)
+        if (qok && !full_last) {
+          for (int i = 0; i <= j; ++i) hcol[i] = hc[i];
+          hcol[j + 1] = est;
+          for (int i = 0; i < j; ++i) {
+            const double a = hcol[i], bb = hcol[i + 1];
+            hcol[i] = cs[i] * a + sn[i] * bb;
+            hcol[i + 1] = -sn[i] * a + cs[i] * bb;
+          }
+          const double a = hcol[j], bb = hcol[j + 1];
+          const double rr = std::hypot(a, bb);
+          const double csj = rr > 0 ? a / rr : 1.0, snj = rr > 0 ? bb / rr : 0.0;
+          if (std::fabs(-snj * g[j]) <= tol) {
+            for (int i = 0; i < j; ++i) H[(size_t)i * m + j] = hcol[i];
+            H[(size_t)j * m + j] = rr;
+            H[(size_t)(j + 1) * m + j] = 0.;
+            cs[j] = csj;
+            sn[j] = snj;
+            g[j + 1] = -snj * g[j];
+            g[j] = csj * g[j];
+            wnorm = est;
+            normalized = done = rotated = true;
+            if (std::getenv("GLS_GMRES_VERBOSE")) printf("  gmres: column %d converges, its projection is skipped\n", j);
+          }
+        }
+        if (rotated) {
+        } else if (qok) {
           HIP_TRY(hipMemcpyAsync(c->coef.p, hc, sizeof(double) * (j + 1), hipMemcpyHostToDevice, s));
           if (j + 1 <= 8) {
-            GLS_TRY(multiaxpy_dots_async(c, w, V, n, j + 1, c->coef.p, true, c->scal2.p, hp2, &h2dev, 1.0 / est));
+            GLS_TRY(multiaxpy_dots_async(c, w, V, n, j + 1, c->coef.p, true, c->scal2.p, hp2, &h2dev, 1.0 / est, x0, x0d,
+                                         x0omega));
+            x0_ready = x0 != nullptr;
           } else {
             HIP_TRY(gls::vec_multiaxpy(w, V, n, j + 1, c->coef.p, 1.0, n, s));
             HIP_TRY(gls::vec_scale(w, 1.0 / est, n, s));
@@ -2071,7 +2126,8 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
             const double est2 = use_est ? std::sqrt(est2sq) : 1.0;
             for (int i = 0; i <= j; ++i) H[(size_t)i * m + j] += est * hp2[i];
             if (j + 1 <= 8) {
-              GLS_TRY(multiaxpy_dots_async(c, w, V, n, j + 1, h2dev, true, c->scal.p, hp1, &hdev, 1.0 / est2));
+              GLS_TRY(multiaxpy_dots_async(c, w, V, n, j + 1, h2dev, true, c->scal.p, hp1, &hdev, 1.0 / est2, x0, x0d,
+                                           x0omega));
             } else {
               HIP_TRY(gls::vec_multiaxpy(w, V, n, j + 1, h2dev, 1.0, n, s));
               if (use_est) HIP_TRY(gls::vec_scale(w, 1.0 / est2, n, s));
@@ -2082,9 +2138,11 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
             double sc = 1.0;                               // v_{j+1} = v' / sc
             if (nn <= 1e-28 * (use_est ? 1.0 : std::max(nrm2, 1e-300))) {
               sc = 0.0;  // breakdown: w lies in span(V) to rounding
+              x0_ready = false;
             } else if (!use_est || std::fabs(nn - 1.0) > 1e-8) {
               sc = std::sqrt(nn);
               HIP_TRY(gls::vec_scale(w, 1.0 / sc, n, s));
+              x0_ready = false;  // w changed after the pass that stored x0: the cycle runs its own update
             }
             H[(size_t)(j + 1) * m + j] = est * est2 * sc;
             for (int i = 0; i <= j; ++i) Gm[(size_t)i * (m + 1) + j + 1] = sc > 0. ? hp1[i] / sc : 0.;
@@ -2150,19 +2208,21 @@ int gls_solve_linear(gls_ctx *c, const double *b, double *x, gls_linear_params *
         if (wnorm > 0) HIP_TRY(gls::vec_scale(w, 1.0 / wnorm, n, s));
       }
       // Givens
-      for (int i = 0; i < j; ++i) {
-        const double a = H[(size_t)i * m + j], bb = H[(size_t)(i + 1) * m + j];
-        H[(size_t)i * m + j] = cs[i] * a + sn[i] * bb;
-        H[(size_t)(i + 1) * m + j] = -sn[i] * a + cs[i] * bb;
+      if (!rotated) {
+        for (int i = 0; i < j; ++i) {
+          const double a = H[(size_t)i * m + j], bb = H[(size_t)(i + 1) * m + j];
+          H[(size_t)i * m + j] = cs[i] * a + sn[i] * bb;
+          H[(size_t)(i + 1) * m + j] = -sn[i] * a + cs[i] * bb;
+        }
+        const double a = H[(size_t)j * m + j], bb = H[(size_t)(j + 1) * m + j];
+        const double rr = std::hypot(a, bb);
+        cs[j] = rr > 0 ? a / rr : 1.0;
+        sn[j] = rr > 0 ? bb / rr : 0.0;
+        H[(size_t)j * m + j] = rr;
+        H[(size_t)(j + 1) * m + j] = 0.;
+        g[j + 1] = -sn[j] * g[j];
+        g[j] = cs[j] * g[j];
       }
-      const double a = H[(size_t)j * m + j], bb = H[(size_t)(j + 1) * m + j];
-      const double rr = std::hypot(a, bb);
-      cs[j] = rr > 0 ? a / rr : 1.0;
-      sn[j] = rr > 0 ? bb / rr : 0.0;
-      H[(size_t)j * m + j] = rr;
-      H[(size_t)(j + 1) * m + j] = 0.;
-      g[j + 1] = -sn[j] * g[j];
-      g[j] = cs[j] * g[j];
       res = std::fabs(g[j + 1]);
       ++it;
       if (getenv("GLS_GMRES_VERBOSE") && (it % 10 == 0 || it == 1))
@@ -2362,6 +2422,8 @@ struct DevicePhysics {
   int rhs_norm(double &r) {
     double r2;
     GLS_TRY(device_dot(c, rhs, rhs, &r2));
+    c->bnorm2_of = rhs;  // the solve that follows takes it (cleared when rhs is evaluated again)
+    c->bnorm2_val = r2;
     r = std::sqrt(r2);
     return GLS_OK;
   }
@@ -2452,6 +2514,7 @@ int gls_newton_solve(gls_ctx *c, double *present, const double *u1, const double
     GLS_TRY(newton_template(ph, prm->tolerance, prm->max_iterations, prm->verbosity, st));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
+  c->bnorm2_of = nullptr;
   prm->newton_iterations = st.outer;
   prm->linear_iterations = st.linear;
   prm->residual_evaluations = st.residuals;

@@ -1387,8 +1387,12 @@ hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *
 // where the coordinate is a cell boundary) in ascending (Morton brick, local node) order, as
 // k_slab_sum_cube does: deterministic. Rows in the coarse level's vmask are zeroed (the V-cycle's
 // vec_set_indexed over con_dofs, which is what vmask lists on a level without hanging nodes).
+// x0 != nullptr: the coarse level's first damped-Jacobi sweep from 0 is stored too, x0 = 0 + omega bc / d
+// (k_jacobi_update's expression on the value just stored to bc: the same bits, without that pass and launch).
 __global__ void __launch_bounds__(256) k_restrict_sum_cube(const double *__restrict__ ev, int nb1, int64_t voff,
-                                                           double *__restrict__ bc, const uint8_t *__restrict__ vmask) {
+                                                           double *__restrict__ bc, const uint8_t *__restrict__ vmask,
+                                                           double *__restrict__ x0, const double *__restrict__ d,
+                                                           double omega) {
   const int NX = 2 * nb1 + 1;
   int bx = blockIdx.x, Z = blockIdx.y;
   if (GLS_SLAB_XCD) {
@@ -1458,17 +1462,22 @@ __global__ void __launch_bounds__(256) k_restrict_sum_cube(const double *__restr
     }
   const int64_t node = X + (int64_t)NX * (Y + (int64_t)NX * Z);
   const unsigned m = vmask ? vmask[node] : 0u;
-  bc[node * 3] = (m & 1u) ? 0.0 : s[0];
-  bc[node * 3 + 1] = (m & 2u) ? 0.0 : s[1];
-  bc[node * 3 + 2] = (m & 4u) ? 0.0 : s[2];
-  bc[voff + node] = s[3];
+  const double r[4] = {(m & 1u) ? 0.0 : s[0], (m & 2u) ? 0.0 : s[1], (m & 4u) ? 0.0 : s[2], s[3]};
+  const int64_t row[4] = {node * 3, node * 3 + 1, node * 3 + 2, voff + node};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) bc[row[q]] = r[q];
+  if (x0) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x0[row[q]] = 0.0 + omega * r[q] / d[row[q]];
+  }
 }
 hipError_t brick_restrict_sum_cube(int nb1, const double *ev, int64_t n_vnodes, double *bc, const uint8_t *vmask,
-                                   hipStream_t s) {
+                                   hipStream_t s, double *x0, const double *d, double omega) {
   const int64_t NX = 2 * (int64_t)nb1 + 1;
-  if (nb1 <= 0 || nb1 > 1023 || !ev || !bc || NX * NX * NX != n_vnodes) return hipErrorInvalidValue;
+  if (nb1 <= 0 || nb1 > 1023 || !ev || !bc || NX * NX * NX != n_vnodes || (x0 && (!d || x0 == bc)))
+    return hipErrorInvalidValue;
   const dim3 g((unsigned)((NX * NX + 255) / 256), (unsigned)NX), b(256);
-  hipLaunchKernelGGL(k_restrict_sum_cube, g, b, 0, s, ev, nb1, 3 * n_vnodes, bc, vmask);
+  hipLaunchKernelGGL(k_restrict_sum_cube, g, b, 0, s, ev, nb1, 3 * n_vnodes, bc, vmask, x0, d, omega);
   return hipGetLastError();
 }
 

@@ -85,6 +85,11 @@ struct gls_ctx {
   DevBuf<double> zbasis;      // restart x n_dofs: M^-1 v_j when the preconditioner is the V-cycle
   DevBuf<double> bicg;        // 7 x n_dofs BiCGStab work vectors (when the GMRES basis is smaller)
   int krylov_m = 0;
+  // Newton's ||rhs||^2 for the solve that follows it (device_dot of that very vector; gls_solve_linear takes it for
+  // its own device_dot(b, b) when b is this pointer and clears it; gls_set_state and the residual evaluations clear
+  // it: the vector is rewritten there)
+  const double *bnorm2_of = nullptr;
+  double bnorm2_val = 0.;
   DevBuf<double> tmp1, tmp2, tmp3, tmp4, tmp5;
   bool use_brick = false;  // sum-factorized brick kernels (3D Qk-Qk, Morton 2x2x2 bricks)
   // brick-boundary node sums without atomics: each brick stores its partial sums of its NBND
@@ -437,10 +442,13 @@ int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double ome
 
 // ---- gls_mg.cpp: the geometric multigrid. mg_prepare re-discretises the levels at the Jacobian's state and factors
 // the coarsest one (no-op unless the state changed); x = V-cycle(b) on level l, and with the replica hierarchy below
-// a distributed fine level (gls_mg_attach_replica)
+// a distributed fine level (gls_mg_attach_replica). x0_ready: x already holds the level's first damped-Jacobi sweep
+// from 0 (stored by the kernel that wrote b), which the cycle then does not launch
 int mg_prepare(gls_ctx *c);
-int mg_vcycle(gls_ctx *c, int l, const double *b, double *x);
+int mg_vcycle(gls_ctx *c, int l, const double *b, double *x, bool x0_ready = false);
 int mg_vcycle_rep2(gls_ctx *c, const double *b, double *x);
+// *d = level 0's diagonal and *omega its damping when mg_vcycle(c, 0, b, x, true) honours x0_ready, else nullptr
+int mg_fine_first_producer(gls_ctx *c, const double **d, double *omega);
 
 // ---- gls_ilu.cpp: the assembled ILU (probe the operator into the CSR values; probe + perturb + factor once per
 // Jacobian state; z = P^T U^-1 L^-1 P v)

@@ -66,9 +66,10 @@ hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *
                                                              //   of y's (launch_pencil_jv_prolong's OpParams::pxp)
 // coarse right-hand side from the bricks' restricted residuals (launch_pencil_jv_restrict: ev [brick][27][4],
 // nb1 fine bricks = coarse cells per direction): bc[node] = sum of the node's <= 8 element-vector entries in
-// ascending (Morton brick, local node) order, rows in the coarse vmask zeroed; n_vnodes = (2 nb1 + 1)^3
+// ascending (Morton brick, local node) order, rows in the coarse vmask zeroed; n_vnodes = (2 nb1 + 1)^3.
+// x0 (with the coarse diagonal d): x0 = 0 + omega bc / d stored too, mg_jacobi_update's first sweep from 0
 hipError_t brick_restrict_sum_cube(int nb1, const double *ev, int64_t n_vnodes, double *bc, const uint8_t *vmask,
-                                   hipStream_t s);
+                                   hipStream_t s, double *x0 = nullptr, const double *d = nullptr, double omega = 0.0);
 bool brick_fused_jacobi_supported(int k);  // the selected brick kernel honours OpParams::jx and ::slabf
 // batched probing: Y[(j - j0) * n_dofs + i] += (J_cell-sum e_j)_i for nprobe unit vectors (MODE_JVQ)
 bool brick_colors_supported(int k);  // colored brick launches (OpParams::bricks) available
@@ -98,10 +99,13 @@ hipError_t vec_multiaxpy(double *w, const double *A, int64_t lda, int nk, const 
 // w = y + a x
 hipError_t vec_waxpy(double *w, const double *y, double a, const double *x, int64_t n, hipStream_t s);
 // w -= sign * sum_k h[k] A[k] (nk <= 8, h on device), fused with out[k] = A[k] . w_new (k < nk, when
-// dots) and out[dots ? nk : 0] = ||w_new||^2, both over the owned rows [0, n1) U [off2, off2 + n2)
+// dots) and out[dots ? nk : 0] = ||w_new||^2, both over the owned rows [0, n1) U [off2, off2 + n2).
+// x0 (with d): x0 = 0 + omega w_new / d too, mg_jacobi_update's first sweep from 0 on w_new (in the same pass by the
+// 16-byte kernel with dots, else by that update launched after it)
 hipError_t vec_multiaxpy_dots(double *w, const double *A, int64_t lda, int nk, const double *h, double sign, int64_t n,
                               int64_t n1, int64_t off2, int64_t n2, bool dots, double scale, double *out,
-                              double *work, hipStream_t s);
+                              double *work, hipStream_t s, double *x0 = nullptr, const double *d = nullptr,
+                              double omega = 0.0);
 // hanging-node constraint lines (CSR): distribute x[dof] = sum w src[master]; condense onto masters
 hipError_t vec_csr_gather_set(double *x, const double *src, const int64_t *dof, const int64_t *off,
                               const int64_t *master, const double *w, int64_t n, hipStream_t s);

@@ -340,12 +340,15 @@ bool mg_fused_restrict_ok(gls_ctx *c, int l) {
 }
 // bc (level l + 1) = R (b - A x) with the constrained coarse rows zeroed (x, b on level l). first_omega > 0
 // (first_sweep_fusable levels): x is not read but formed and stored as the first damped-Jacobi sweep from 0,
-// as in jacobian_apply_f32
-int mg_residual_restrict_fused(gls_ctx *c, int l, double *x, const double *b, double *bc, double first_omega = 0.0) {
+// as in jacobian_apply_f32. xc0 (level l + 1, with that level's damping): the sum also stores that level's first
+// damped-Jacobi sweep from 0, xc0 = 0 + omega_c bc / D_c
+int mg_residual_restrict_fused(gls_ctx *c, int l, double *x, const double *b, double *bc, double first_omega = 0.0,
+                               double *xc0 = nullptr, double omega_c = 0.0) {
   gls_ctx *g = c->mg.lev[(size_t)l], *h = c->mg.lev[(size_t)l + 1];
   if (!g->u) return set_err(GLS_EINVAL, "gls_set_state was not called");
   GLS_TRY(ensure_diag(g));
   GLS_TRY(ensure_qdata32(g, !g->smooth_oseen));
+  if (xc0) GLS_TRY(ensure_diag(h));
   gls::OpParams P = make_params(g, true);
   P.qdf = g->qdata32.p;
   P.oseen = g->smooth_oseen ? 1 : 0;
@@ -364,7 +367,8 @@ int mg_residual_restrict_fused(gls_ctx *c, int l, double *x, const double *b, do
     HIP_TRY(gls::launch_pencil_jv_restrict(P, g->tables, c->stream));
   }
   TimedLaunch t(g, 5);
-  HIP_TRY(gls::brick_restrict_sum_cube(g->cube_nb1, P.slab, h->n_vnodes, bc, h->vmask.p, c->stream));
+  HIP_TRY(gls::brick_restrict_sum_cube(g->cube_nb1, P.slab, h->n_vnodes, bc, h->vmask.p, c->stream, xc0,
+                                       xc0 ? h->diag.p : nullptr, omega_c));
   return GLS_OK;
 }
 
@@ -456,16 +460,17 @@ int coarse_graph_capture(gls_ctx *c, gls_ctx *g, const double *b, double *x, dou
 }
 
 // x = pre smoothing sweeps from x = 0 on level g: its ILU(0) when zs (the scratch) is given, else damped Jacobi;
-// residual: then y = b - A x (y is the sweeps' scratch before that)
+// residual: then y = b - A x (y is the sweeps' scratch before that). x0_ready: x already holds the first damped-Jacobi
+// sweep from 0, stored by the kernel that wrote b (mg_first_producer_ok)
 int mg_presmooth(gls_ctx *g, hipStream_t s, int pre, double om, double *zs, const double *b, double *x, double *y,
-                 bool residual) {
+                 bool residual, bool x0_ready = false) {
   const int64_t n = g->n_dofs;
   if (pre > 0 && zs) {
     GLS_TRY(ensure_ilu(g));
     GLS_TRY(apply_ilu(g, b, x));  // first sweep from x = 0: x = M^-1 b
     for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(g, x, b, y, om, zs));
   } else if (pre > 0) {
-    HIP_TRY(gls::mg_jacobi_update(x, b, nullptr, g->diag.p, om, n, 1, s));  // first sweep from x = 0
+    if (!x0_ready) HIP_TRY(gls::mg_jacobi_update(x, b, nullptr, g->diag.p, om, n, 1, s));  // first sweep from x = 0
     for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(g, x, b, y, om));
   } else {
     HIP_TRY(gls::vec_fill(x, n, 0.0, s));
@@ -474,6 +479,25 @@ int mg_presmooth(gls_ctx *g, hipStream_t s, int pre, double om, double *zs, cons
   if (pre > 0) return smoother_apply(g, x, y, b);  // y = b - A x
   HIP_TRY(gls::vec_copy(y, b, n, s));  // x = 0: the residual is b
   return GLS_OK;
+}
+// Level l's cycle starts with a damped-Jacobi sweep from 0 as a launch of its own (mg_presmooth's update; not the
+// exact solve, the replica, the coarse graph, ILU smoothing or the opt-in first_sweep_fusable path), so the kernel
+// that writes the level's right-hand side may store x = 0 + omega b / D with it and the cycle skip that launch:
+// the same expression on the same operands, bitwise the separate update. GLS_MG_FIRST_PRODUCER=0 (read per call) or
+// GLS_MG_NO_FUSE keep the update launches.
+bool mg_first_producer_ok(gls_ctx *c, int l) {
+  auto &mg = c->mg;
+  const int L = (int)mg.lev.size();
+  if (l < 0 || l >= L) return false;
+  const char *e = std::getenv("GLS_MG_FIRST_PRODUCER");
+  if ((e && std::atoi(e) == 0) || std::getenv("GLS_MG_NO_FUSE") != nullptr) return false;
+  gls_ctx *g = mg.lev[(size_t)l];
+  if (l == L - 1 && (mg.replica || mg.coarse.ok)) return false;
+  const int pre = l == L - 1 ? mg.csweeps : mg.lpre[(size_t)l];
+  if (pre < 1 || g->dist.on || g->stream != c->stream) return false;
+  if (l == L - 1 && l > 0 && pre > 1 && coarse_graph_eligible(c, g, mgbuf(c, l, MB_B), mgbuf(c, l, MB_X))) return false;
+  if (pre == 1 && l < L - 1 && first_sweep_fusable(g)) return false;
+  return !(mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only);
 }
 // the coarsest level's exact solve; the first one of a state waits for the side stream's factorization
 int mg_coarse_solve(gls_ctx *c, gls_ctx *g, const double *b, double *x) {
@@ -514,8 +538,21 @@ int mg_vcycle_rep2(gls_ctx *c, const double *b, double *x) {
   return GLS_OK;
 }
 
+// The fine level's cycle may take its first sweep from the kernel that writes its right-hand side (GMRES's
+// projection): the plain V-cycle on one rank (not rep2; mg_first_producer_ok covers the rest). *d = nullptr: no
+int mg_fine_first_producer(gls_ctx *c, const double **d, double *omega) {
+  *d = nullptr;
+  auto &mg = c->mg;
+  if (!mg.on || mg.rep_csr || mg.lev.empty() || c->dist.on || !mg_first_producer_ok(c, 0)) return GLS_OK;
+  gls_ctx *g = mg.lev[0];
+  GLS_TRY(ensure_diag(g));
+  *d = g->diag.p;
+  *omega = mg.lev.size() == 1 ? mg.comega : mg.omega;
+  return GLS_OK;
+}
+
 // x = V-cycle(b) on level l (x, b are level-l vectors)
-int mg_vcycle(gls_ctx *c, int l, const double *b, double *x) {
+int mg_vcycle(gls_ctx *c, int l, const double *b, double *x, bool x0_ready) {
   auto &mg = c->mg;
   const int L = (int)mg.lev.size();
   gls_ctx *g = mg.lev[l];
@@ -547,19 +584,22 @@ int mg_vcycle(gls_ctx *c, int l, const double *b, double *x) {
   double *zs = mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only ? mgbuf(c, l, MB_BOX) : nullptr;  // ILU smoothing scratch
   // bc = R (b - A x), constrained rows zeroed, in one J.v + one sum (first_fused: x = omega D^-1 b formed there too)
   const bool fused_restrict = l < L - 1 && pre > 0 && mg_fused_restrict_ok(c, l);
-  if (!first_fused) GLS_TRY(mg_presmooth(g, s, pre, om, zs, b, x, y, l < L - 1 && !fused_restrict));
+  if (!first_fused) GLS_TRY(mg_presmooth(g, s, pre, om, zs, b, x, y, l < L - 1 && !fused_restrict, x0_ready));
   if (l == L - 1) return GLS_OK;
   // residual -> coarse right-hand side: restrict the owned rows, export-add coarse ghost rows
   gls_ctx *h = mg.lev[l + 1];
   double *bc = mgbuf(c, l + 1, MB_B), *xc = mgbuf(c, l + 1, MB_X);
+  // the restriction's sum stores level l + 1's first sweep from 0 with its right-hand side
+  const bool xc_ready = fused_restrict && mg_first_producer_ok(c, l + 1);
   if (fused_restrict) {
-    GLS_TRY(mg_residual_restrict_fused(c, l, x, b, bc, first_fused ? om : 0.0));
+    GLS_TRY(mg_residual_restrict_fused(c, l, x, b, bc, first_fused ? om : 0.0, xc_ready ? xc : nullptr,
+                                       l + 1 == L - 1 ? mg.comega : mg.omega));
   } else {
     if (first_fused) GLS_TRY(jacobian_apply_f32(g, x, y, b, om, g->smooth_oseen));  // x = omega D^-1 b, y = b - A x
     GLS_TRY(mg_restrict(c, l, y, bc));
     HIP_TRY(gls::vec_set_indexed(bc, h->con_dofs.p, nullptr, (int64_t)h->con_dofs.n, s));
   }
-  GLS_TRY(mg_vcycle(c, l + 1, bc, xc));
+  GLS_TRY(mg_vcycle(c, l + 1, bc, xc, xc_ready));
   // prolongate the coarse correction (ghost values imported first). x += P xc in the transfer's
   // store on one rank: the coarse correction vanishes on the coarse Dirichlet rows (zero rhs rows,
   // D_c-scaled sweeps) and the nested Qk interpolation maps them onto the fine Dirichlet rows, so

@@ -231,10 +231,14 @@ __global__ void __launch_bounds__(kBlock) k_multidot16(const double *__restrict_
     work[threadIdx.x * gridDim.x + blockIdx.x] = t;
   }
 }
-template <int NK, bool DOTS>
+// X0: the new w is the right-hand side of the next V-cycle, whose first damped-Jacobi sweep from 0 is stored with it,
+// x0 = 0 + omega w_new / d (k_jacobi_update's expression on the value stored to w: the same bits)
+template <int NK, bool DOTS, bool X0 = false>
 __global__ void __launch_bounds__(kBlock) k_multiaxpy_dot16(double *__restrict__ w, const double *__restrict__ A,
                                                             int64_t lda, const double *__restrict__ h, double sign,
-                                                            int64_t n, double scale, double *work) {
+                                                            int64_t n, double scale, double *work,
+                                                            double *__restrict__ x0 = nullptr,
+                                                            const double *__restrict__ d = nullptr, double omega = 0.0) {
   constexpr int ND = (DOTS ? NK : 0) + 1;
   double hk[NK], acc[ND];
 #pragma unroll
@@ -262,15 +266,21 @@ __global__ void __launch_bounds__(kBlock) k_multiaxpy_dot16(double *__restrict__
       a0[k] = a.x;
       a1[k] = a.y;
     }
+    dbl2 di = {1.0, 1.0};
+    if constexpr (X0) di = __builtin_nontemporal_load(reinterpret_cast<const dbl2 *>(d) + p);  // in flight with the basis
     const dbl2 wi = reinterpret_cast<const dbl2 *>(w)[p];
     const double o0 = row(wi.x, a0), o1 = row(wi.y, a1);
     reinterpret_cast<dbl2 *>(w)[p] = dbl2{o0, o1};
+    if constexpr (X0)
+      __builtin_nontemporal_store(dbl2{0.0 + omega * o0 / di.x, 0.0 + omega * o1 / di.y}, reinterpret_cast<dbl2 *>(x0) + p);
   }
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
     double a[NK];
 #pragma unroll
     for (int k = 0; k < NK; ++k) a[k] = A[k * lda + n - 1];
-    w[n - 1] = row(w[n - 1], a);
+    const double o = row(w[n - 1], a);
+    w[n - 1] = o;
+    if constexpr (X0) x0[n - 1] = 0.0 + omega * o / d[n - 1];
   }
   __shared__ double red[ND][kBlock / 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -553,10 +563,12 @@ hipError_t vec_waxpy(double *w, const double *y, double a, const double *x, int6
 
 hipError_t vec_multiaxpy_dots(double *w, const double *A, int64_t lda, int nk, const double *h, double sign, int64_t n,
                               int64_t n1, int64_t off2, int64_t n2, bool dots, double scale, double *out, double *work,
-                              hipStream_t s) {
-  if (nk < 1 || nk > kDotChunk) return hipErrorInvalidValue;
+                              hipStream_t s, double *x0, const double *d, double omega) {
+  if (nk < 1 || nk > kDotChunk || (x0 && (!d || x0 == w))) return hipErrorInvalidValue;
   const int nb = grid_for(n);
   const bool v16 = vec16(A, lda, w, n, n1, n2);
+  // x0 in the same pass: the 16-byte kernel with the dots; any other variant is followed by the separate update
+  const bool x16 = x0 && v16 && dots && ((uintptr_t)x0 % 16) == 0 && ((uintptr_t)d % 16) == 0;
   switch (nk * 2 + (dots ? 1 : 0)) {
 #define MX(M)                                                                                                         \
   case 2 * M:                                                                                                         \
@@ -567,7 +579,10 @@ hipError_t vec_multiaxpy_dots(double *w, const double *A, int64_t lda, int nk, c
                          scale, work);                                                                                \
     break;                                                                                                            \
   case 2 * M + 1:                                                                                                     \
-    if (v16)                                                                                                          \
+    if (x16)                                                                                                          \
+      hipLaunchKernelGGL((k_multiaxpy_dot16<M, true, true>), dim3(nb), dim3(kBlock), 0, s, w, A, lda, h, sign, n, scale, \
+                         work, x0, d, omega);                                                                         \
+    else if (v16)                                                                                                     \
       hipLaunchKernelGGL((k_multiaxpy_dot16<M, true>), dim3(nb), dim3(kBlock), 0, s, w, A, lda, h, sign, n, scale, work); \
     else                                                                                                              \
       hipLaunchKernelGGL((k_multiaxpy_dot<M, true>), dim3(nb), dim3(kBlock), 0, s, w, A, lda, h, sign, n, n1, off2, n2, \
@@ -577,6 +592,7 @@ hipError_t vec_multiaxpy_dots(double *w, const double *A, int64_t lda, int nk, c
 #undef MX
   }
   hipLaunchKernelGGL(k_reduce_rows, dim3(dots ? nk + 1 : 1), dim3(kBlock), 0, s, work, nb, out);
+  if (x0 && !x16) return mg_jacobi_update(x0, w, nullptr, d, omega, n, 1, s);
   return hipGetLastError();
 }
 
