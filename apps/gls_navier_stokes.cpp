@@ -2042,6 +2042,35 @@ struct Solver {
     }
   }
 
+  // The L2 projection on the device (--ic-eval device: gls_projection_plan_create / gls_l2_projection) straight into
+  // d_present: no host vector, no upload. The plan is used once per run and released at once. What the library does
+  // not serve (GLS_EINVAL: 2D Q3, curved slip walls -- their lines --, an expression it cannot run) and --np (every
+  // rank projects on its copy) take the host path, said once on stderr.
+  bool ic_device = false;  // --ic-eval
+  bool l2_projection_device(gls_projection_info &info) {
+    if (!ic_device) return false;
+    if (world != 1) {
+      if (rank == 0) std::fprintf(stderr, "initial condition: host projection (--np: every rank projects on its copy)\n");
+      return false;
+    }
+    const gls_mesh_desc D = mesh_desc();
+    gls_projection_plan *plan = nullptr;
+    int rc = gls_projection_plan_create(ctx, &D, &plan);  // the library decides what it has a kernel for
+    if (rc == GLS_OK) {
+      need_dev();
+      rc = gls_l2_projection(ctx, plan, P.ic.e, time, d_present, &info);
+      gls_projection_plan_destroy(plan);
+    }
+    if (rc == GLS_EINVAL) {
+      std::fprintf(stderr, "initial condition: host projection (%s)\n", gls_last_error());
+      return false;
+    }
+    ck(rc, "gls_l2_projection");
+    dev_changed();
+    std::fprintf(stderr, "initial condition: on the device (gls_l2_projection), %lld cells\n", (long long)m.nc);
+    return true;
+  }
+
   // --np diagnostics (GLS_NP_CHECK): the gathered distributed residual at the current state against
   // the residual of a whole-mesh context on rank 0; the largest differences are printed to stderr
   void check_distributed_residual(const double ts[4]) {
@@ -3106,8 +3135,23 @@ struct Solver {
       host_changed();
       if (P.ic_type == "viscous") solve_nonlinear(GLS_STEADY, P.ic_nu);
     } else if (P.ic_type == "L2projection") {
-      l2_projection(P.ic, present);
-      host_changed();
+      // GLS_IC_SPLIT=1: the host clock of the initial condition (and the device solve's figures) on stderr
+      static const bool split = std::getenv("GLS_IC_SPLIT") != nullptr;
+      const auto t0 = std::chrono::steady_clock::now();
+      gls_projection_info info = {0, 0.0};
+      const bool dev = l2_projection_device(info);
+      if (!dev) {
+        l2_projection(P.ic, present);
+        host_changed();
+      }
+      if (split && rank == 0) {
+        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (dev)
+          std::fprintf(stderr, "initial condition: L2 projection on the device %.6f s, %d CG iterations, relative residual %.3e\n",
+                       dt, info.iterations, info.relative_residual);
+        else
+          std::fprintf(stderr, "initial condition: L2 projection on the host %.6f s\n", dt);
+      }
     } else {
       die("initial condition type '%s' is not supported", P.ic_type.c_str());
     }
@@ -3185,9 +3229,10 @@ int main(int argc, char **argv) {
   // 0 = one block), --ilu-order cm|multicolor (gls_ilu_set_options), --dump DIR (every iteration's
   // final state for the pipeline tests), --output-eval host|device (the VTU point data from the host vector or,
   // the default, on the device from the device-resident solution), --error-eval host|device (the L2 error against
-  // the analytical solution from the host vector, the default, or on the device).
+  // the analytical solution from the host vector, the default, or on the device), --ic-eval host|device (the
+  // L2projection initial condition by the host conjugate gradients, the default, or on the device).
   int dim = 0;
-  bool output_device = true, error_device = false;
+  bool output_device = true, error_device = false, ic_device = false;
   bool mg = true, stats = false;
   int64_t ilu_block = -1;
   int ilu_order = -1;
@@ -3228,6 +3273,11 @@ int main(int argc, char **argv) {
       const char *o = argv[++i];
       if (std::strcmp(o, "host") && std::strcmp(o, "device")) die("--error-eval %s: host or device", o);
       error_device = !std::strcmp(o, "device");
+    }
+    else if (!std::strcmp(argv[i], "--ic-eval") && i + 1 < argc) {
+      const char *o = argv[++i];
+      if (std::strcmp(o, "host") && std::strcmp(o, "device")) die("--ic-eval %s: host or device", o);
+      ic_device = !std::strcmp(o, "device");
     }
     else if (argv[i][0] != '-') file = argv[i];
     else die("unknown option %s", argv[i]);
@@ -3284,6 +3334,7 @@ int main(int argc, char **argv) {
   if (dump) s.dump_dir = dump;
   s.output_device = output_device;
   s.error_device = error_device;
+  s.ic_device = ic_device;
   s.run();
   if (np_ranks > 1) {
     g_comm.barrier("end");

@@ -936,6 +936,39 @@ int gls_error_plan_create(gls_ctx *ctx, const gls_mesh_desc *mesh, const gls_exp
 int gls_error_plan_destroy(gls_error_plan *plan);
 int gls_l2_error(gls_ctx *ctx, gls_error_plan *plan, const double *sol, double time, double out[2]);
 
+/* The L2 projection of a function onto the velocity-pressure space on the device (the reference's
+ * set_initial_condition(L2projection): assemble_L2_projection + solve_system_GMRES(.., 1e-15, 1e-15),
+ * gls_navier_stokes.cc:795-803, 830-914): the consistent mass matrix M (block diagonal per component, QGauss(k+1))
+ * is never assembled. One launch per product integrates the cells' values back to their nodes by sum factorization
+ * and writes element vectors; one ordered gather sums every node's slots in ascending cell order (no atomics).
+ * gls_projection_plan_create uploads the geometry (box cells: cell_x0 / cell_h; mapped cells: cell_support), the 1D
+ * tables, the node -> (cell, slot) incidence, and computes the diagonal of M (one launch); mesh must be the
+ * description the context was created from (dim, k, kp, n_cells and map_degree are checked); rebuild the plan after
+ * an adaptation. Every layout of a conforming context (brick, per-cell box, mapped, periodic: identified nodes are
+ * one id) gives the same bits. Kernels exist for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}, box and mapped
+ * (map_degree <= 3); anything else (2D Q3), a distributed context and a context with hanging or slip lines
+ * (gls_set_hanging) are GLS_EINVAL at gls_projection_plan_create, with the limit named in gls_last_error().
+ *   gls_mass_apply:     y = M x on DEVICE vectors in the context's DoF layout, no constraint mask (x != y)
+ *   gls_mass_diagonal:  d = diag(M), the diagonal gls_l2_projection preconditions with (DEVICE vector)
+ *   gls_l2_projection:  x = the L2 projection of f(x, t) at `time` (variables: the dim coordinates, then t; exactly
+ *                       dim + 1 components u.., p; anything else is GLS_EINVAL), with the context's Dirichlet set
+ *                       (gls_set_dirichlet) held fixed at its values, which is what distribute_local_to_global with
+ *                       nonzero_constraints and distribute() yield. Jacobi-preconditioned conjugate gradients in
+ *                       FP64 on the context's stream, from the Dirichlet values and zero elsewhere, on the free
+ *                       rows, until |r| <= 1e-15 |b|; at most 10000 iterations, GLS_ENOCONV with the count in
+ *                       gls_last_error() otherwise (info is filled either way). The right-hand side is integrated
+ *                       on the device from the expression's bytecode at the Gauss points (gls_expr_eval_device's
+ *                       interpreter and stack limit). Two calls on the same input are bitwise equal. Synchronizes
+ *                       the stream (two scalar read-backs per iteration). */
+typedef struct gls_projection_plan gls_projection_plan;
+typedef struct { int iterations; double relative_residual; } gls_projection_info;
+int gls_projection_plan_create(gls_ctx *ctx, const gls_mesh_desc *mesh, gls_projection_plan **plan);
+int gls_projection_plan_destroy(gls_projection_plan *plan);
+int gls_mass_apply(gls_ctx *ctx, gls_projection_plan *plan, const double *x, double *y);
+int gls_mass_diagonal(gls_ctx *ctx, gls_projection_plan *plan, double *d);
+int gls_l2_projection(gls_ctx *ctx, gls_projection_plan *plan, const gls_expr *f, double time, double *x,
+                      gls_projection_info *info);
+
 /* Output: NavierStokesBase::write_output_results (navier_stokes_base.cc:998-1086) — one patch per
  * cell with `subdivision` intervals (Lagrange cells when k > 1), point data velocity, pressure,
  * subdomain, vorticity, q_criterion [, velocity_eulerian when mesh->srf]; solution is a HOST

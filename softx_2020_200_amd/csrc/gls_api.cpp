@@ -21,6 +21,7 @@
 #include <set>
 
 #include "gls_ctx.hpp"
+#include "gls_incidence.hpp"
 
 using namespace gls_impl;
 
@@ -751,21 +752,13 @@ int ensure_element_maps(gls_ctx *c) {
     HIP_TRY(hipMemcpy(cp.data(), c->cell_pnodes.p, cp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
   const std::vector<int32_t> &pn = c->cell_pnodes.p ? cp : cv;
-  std::vector<int64_t> voff((size_t)c->n_vnodes + 1, 0), poff((size_t)c->n_pnodes + 1, 0);
-  for (int64_t e = 0; e < (int64_t)c->n_cells * nv; ++e) ++voff[(size_t)cv[(size_t)e] + 1];
-  for (int64_t e = 0; e < (int64_t)c->n_cells * np; ++e) ++poff[(size_t)pn[(size_t)e] + 1];
-  for (size_t i = 1; i < voff.size(); ++i) voff[i] += voff[i - 1];
-  for (size_t i = 1; i < poff.size(); ++i) poff[i] += poff[i - 1];
-  std::vector<int64_t> vslot((size_t)voff.back()), pslot((size_t)poff.back());
-  std::vector<int64_t> vf(voff.begin(), voff.end() - 1), pf(poff.begin(), poff.end() - 1);
-  for (int64_t cell = 0; cell < c->n_cells; ++cell) {
-    for (int a = 0; a < nv; ++a) vslot[(size_t)vf[(size_t)cv[(size_t)(cell * nv + a)]]++] = cell * el + (int64_t)a * dim;
-    for (int a = 0; a < np; ++a) pslot[(size_t)pf[(size_t)pn[(size_t)(cell * np + a)]]++] = cell * el + (int64_t)nv * dim + a;
-  }
-  GLS_TRY(c->ev_voff.upload(voff.data(), voff.size()));
-  GLS_TRY(c->ev_vslot.upload(vslot.data(), std::max<size_t>(vslot.size(), 1)));
-  GLS_TRY(c->ev_poff.upload(poff.data(), poff.size()));
-  GLS_TRY(c->ev_pslot.upload(pslot.data(), std::max<size_t>(pslot.size(), 1)));
+  ElementIncidence I;
+  if (!element_incidence(c->n_cells, dim, nv, np, c->n_vnodes, c->n_pnodes, cv.data(), pn.data(), I))
+    return set_err(GLS_EINVAL, "element maps: a cell's node id is out of range");
+  GLS_TRY(c->ev_voff.upload(I.voff.data(), I.voff.size()));
+  GLS_TRY(c->ev_vslot.upload(I.vslot.data(), std::max<size_t>(I.vslot.size(), 1)));
+  GLS_TRY(c->ev_poff.upload(I.poff.data(), I.poff.size()));
+  GLS_TRY(c->ev_pslot.upload(I.pslot.data(), std::max<size_t>(I.pslot.size(), 1)));
   return c->ev.alloc((size_t)c->n_cells * el);
 }
 }  // namespace gls_impl

@@ -96,4 +96,48 @@ __device__ __forceinline__ void finish(const double *f, int n, int np1, const in
   }
 }
 
+// ---- the transposed sweeps (gls_mass.hip): the lanes' weighted point values q [np1^dim] (x fastest, one array per
+// field and cell, cs apart like the regions) integrated back against the basis, through the same regions in the
+// reverse order: q -> B -> A -> nodal sums (3D), q -> A -> nodal sums (2D). Values only; the caller separates the
+// steps by __syncthreads().
+// last direction: B[t0, t1, a2] = sum_t2 V[t2][a2] q[t0, t1, t2] (3D), A[t0, a1] = sum_t1 V[t1][a1] q[t0, t1] (2D)
+template <int DIM>
+__device__ __forceinline__ void sweep_t_last(double *f, const double *q, int cs, int ncl, int n, int np1,
+                                             const double *V) {
+  const int nod = opow(n, DIM), ia = field_items_a(DIM, n, np1), items = DIM == 3 ? np1 * np1 * n : ia;
+  const int plane = opow(np1, DIM - 1);  // points per value of the last coordinate
+  for (int i = threadIdx.x; i < ncl * items; i += blockDim.x) {
+    const int cl = i / items, r = i - cl * items, pt = r % plane, a = r / plane;
+    const double *src = q + cl * cs + pt;
+    double v = 0.0;
+    for (int t = 0; t < np1; ++t) v += V[t * n + a] * src[plane * t];
+    f[cl * cs + nod + (DIM == 3 ? ia : 0) + r] = v;
+  }
+}
+
+// y direction (3D): A[t0, a1, a2] = sum_t1 V[t1][a1] B[t0, t1, a2]
+__device__ __forceinline__ void sweep_t_b(double *f, int cs, int ncl, int n, int np1, const double *V) {
+  const int nod = n * n * n, ia = np1 * n * n;
+  for (int i = threadIdx.x; i < ncl * ia; i += blockDim.x) {
+    const int cl = i / ia, r = i - cl * ia, t0 = r % np1, a1 = (r / np1) % n, a2 = r / (np1 * n);
+    const double *b = f + cl * cs + nod + ia + t0 + np1 * np1 * a2;
+    double v = 0.0;
+    for (int t = 0; t < np1; ++t) v += V[t * n + a1] * b[np1 * t];
+    f[cl * cs + nod + r] = v;
+  }
+}
+
+// x direction: nodal[a0, rest] = sum_t0 V[t0][a0] A[t0, rest]
+template <int DIM>
+__device__ __forceinline__ void sweep_t_a(double *f, int cs, int ncl, int n, int np1, const double *V) {
+  const int nod = opow(n, DIM);
+  for (int i = threadIdx.x; i < ncl * nod; i += blockDim.x) {
+    const int cl = i / nod, r = i - cl * nod, a0 = r % n, rest = r / n;
+    const double *a = f + cl * cs + nod + np1 * rest;
+    double v = 0.0;
+    for (int t = 0; t < np1; ++t) v += V[t * n + a0] * a[t];
+    f[cl * cs + r] = v;
+  }
+}
+
 }  // namespace gls

@@ -262,6 +262,21 @@ hipError_t launch_l2_error(int dim, int k, int kp, int map_degree, const int32_t
                            int64_t n_cells, const expr::DeviceProgram &exact, double time, double volume, double *partial,
                            double *out, hipStream_t s);
 
+// ---- the consistent mass matrix, matrix-free (gls_mass.hip): QGauss(k+1), one lane per quadrature point, the dim
+// velocity components and the pressure as scalar fields. One launch writes the element vectors ev [n_cells][NV dim +
+// NP] in the per-cell kernels' layout (gather_element_vectors sums them per node in a fixed order): kMassApply
+// M_e x_e of the device vector x, kMassRhs int phi f(x, time) JxW with f's dim + 1 components from the device
+// interpreter, kMassDiag sum_q phi_a(q)^2 JxW. x0h / support as for the output fields; tab = Vv [k+1][k+1] | Vp
+// [k+1][kp+1] | xq [k+1] | wq [k+1] | Vv^2 | Vp^2 | Vm [k+1][map_degree+1] | Dm (the last two for mapped cells only)
+// at the Gauss abscissae. Instantiated for dim 2, 3 and (k, kp) in {(1,1), (2,1), (2,2)}, box and mapped
+// (map_degree <= 3); max_stack <= 16 (0: no expression).
+constexpr int kMassApply = 0, kMassRhs = 1, kMassDiag = 2;
+bool mass_supported(int dim, int k, int kp, int map_degree, int max_stack);
+hipError_t launch_mass(int mode, int dim, int k, int kp, int map_degree, const int32_t *cell_vnodes,
+                       const int32_t *cell_pnodes, const double *x, int64_t pbase, const double *x0h,
+                       const double *support, const double *tab, int64_t n_cells, const expr::DeviceProgram *f,
+                       double time, double *ev, hipStream_t s);
+
 // ---- geometric multigrid (gls_mg_kernels.hip): nested Qk node lattices (boxes), k <= 2
 hipError_t mg_inject(const double *fine, double *coarse, const int nf[3], const int nc[3], hipStream_t s);
 // one-pass 3D transfer with per-axis tap tables [n_out][5] (index, weight) and tap counts [n_out]

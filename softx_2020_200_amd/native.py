@@ -36,6 +36,8 @@ EXPORTS = [
     "gls_prm_parse", "gls_prm_get", "gls_prm_n_entries", "gls_prm_entry", "gls_prm_destroy",
     "gls_expr_create", "gls_expr_n_components", "gls_expr_eval", "gls_expr_destroy", "gls_expr_eval_device",
     "gls_error_plan_create", "gls_error_plan_destroy", "gls_l2_error",
+    "gls_projection_plan_create", "gls_projection_plan_destroy", "gls_mass_apply", "gls_mass_diagonal",
+    "gls_l2_projection",
     "gls_vtu_write", "gls_pvtu_write", "gls_pvd_write",
     "gls_set_hanging", "gls_mesh_refined_create", "gls_mesh_refined_destroy", "gls_octree_create", "gls_octree_destroy", "gls_octree_info",
     "gls_octree_cells", "gls_octree_adapt", "gls_octree_prepare", "gls_octree_mesh", "gls_octree_mesh_destroy", "gls_octree_transfer", "gls_octree_faces", "gls_kelly_estimate_faces",
@@ -111,6 +113,10 @@ class TimeControlParams(C.Structure):
 
 
 OUTPUT_CONTROL = {"iteration": 0, "time": 1}
+
+
+class ProjectionInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("relative_residual", C.c_double)]
 
 
 class RefinedMesh(C.Structure):
@@ -242,6 +248,11 @@ def load():
     L.gls_error_plan_create.argtypes = [vp, C.POINTER(MeshDesc), vp, C.POINTER(vp)]
     L.gls_error_plan_destroy.argtypes = [vp]
     L.gls_l2_error.argtypes = [vp, vp, vp, C.c_double, d]
+    L.gls_projection_plan_create.argtypes = [vp, C.POINTER(MeshDesc), C.POINTER(vp)]
+    L.gls_projection_plan_destroy.argtypes = [vp]
+    L.gls_mass_apply.argtypes = [vp, vp, vp, vp]
+    L.gls_mass_diagonal.argtypes = [vp, vp, vp]
+    L.gls_l2_projection.argtypes = [vp, vp, vp, C.c_double, vp, C.POINTER(ProjectionInfo)]
     L.gls_time_control_create.argtypes = [C.POINTER(TimeControlParams), C.POINTER(vp)]
     L.gls_time_control_destroy.argtypes = [vp]
     L.gls_time_control_destroy.restype = None
@@ -1021,6 +1032,12 @@ class GLSContext:
         after an adaptation."""
         return ErrorPlan(self, mesh, expr)
 
+    def projection_plan(self, mesh):
+        """The matrix-free consistent mass operator and the L2 projection on this context's cells
+        (gls_projection_plan_create): mesh is the mesh the context was created from. Conforming contexts only (no
+        hanging or slip lines); make a new plan after an adaptation."""
+        return ProjectionPlan(self, mesh)
+
     def mg_transfer(self, level, direction, v, out):
         """Restrict (direction 0: level -> level+1) or prolongate (1: level+1 -> level) a device vector."""
         check(self.L.gls_mg_transfer(self.h, int(level), int(direction), _ptr(v), _ptr(out)), "gls_mg_transfer")
@@ -1188,6 +1205,58 @@ class ErrorPlan:
         out = np.zeros(2)
         check(self.L.gls_l2_error(self.ctx.h, self.h, _ptr(sol), float(time), _dp(out)), "gls_l2_error")
         return float(out[0]), float(out[1])
+
+
+class ProjectionPlan:
+    """One gls_projection_plan: the Gauss-point geometry and tables of one mesh, the node -> slot incidence and the
+    mass diagonal on the device."""
+
+    def __init__(self, ctx, mesh):
+        self.ctx, self.L = ctx, ctx.L
+        D, keep = mesh_desc(mesh)
+        h = C.c_void_p()
+        check(self.L.gls_projection_plan_create(ctx.h, C.byref(D), C.byref(h)), "gls_projection_plan_create")
+        self.h = h
+        self.iterations, self.relative_residual = 0, 0.0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gls_projection_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def mass_apply(self, x, out=None):
+        """y = M x of a device vector, no constraint mask (gls_mass_apply)"""
+        import torch
+        out = torch.empty_like(x) if out is None else out
+        check(self.L.gls_mass_apply(self.ctx.h, self.h, _ptr(x), _ptr(out)), "gls_mass_apply")
+        return out
+
+    def diagonal(self):
+        """diag(M) as a device vector: what project() preconditions with (gls_mass_diagonal)"""
+        import torch
+        out = torch.empty(self.ctx.n_dofs, dtype=torch.float64, device="cuda")
+        check(self.L.gls_mass_diagonal(self.ctx.h, self.h, _ptr(out)), "gls_mass_diagonal")
+        return out
+
+    def project(self, expr, time=0.0, out=None):
+        """The L2 projection of an io.Expr over x, y [, z], t with dim + 1 components (u.., p) as a device vector,
+        the context's Dirichlet set held fixed (gls_l2_projection). The iteration count and the final relative
+        residual of the conjugate gradients are left in .iterations / .relative_residual."""
+        import torch
+        out = torch.empty(self.ctx.n_dofs, dtype=torch.float64, device="cuda") if out is None else out
+        info = ProjectionInfo()
+        try:
+            check(self.L.gls_l2_projection(self.ctx.h, self.h, expr.h, float(time), _ptr(out), C.byref(info)),
+                  "gls_l2_projection")
+        finally:
+            self.iterations, self.relative_residual = int(info.iterations), float(info.relative_residual)
+        return out
 
 
 class UMesh:
