@@ -533,6 +533,7 @@ gls::OpParams make_params(gls_ctx *c, bool jac) {
   P.gq = c->gq.p;
   P.force_q = c->force_q.p;
   P.vmask = c->vmask.p;
+  P.cube_nb1 = c->k == 2 ? c->cube_nb1 : 0;  // the pencil kernels' lattice gather (OpParams::cube_gather)
   P.u = c->u;
   P.h1 = c->u1 ? c->u1 : c->u;
   P.h2 = c->u2 ? c->u2 : c->u;

@@ -142,6 +142,20 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   // first cell of a brick: 8 b on the cube; the listed cell on an adapted forest's sibling groups
   auto cell0 = [&](int b) -> int64_t { return P.brick_cell0 ? (int64_t)P.brick_cell0[b] : (int64_t)b * 8; };
   const int64_t voff = (int64_t)3 * P.n_vnodes;
+  // node (X, Y, Z) of brick b's 5^3 lattice. On the verified hyper_cube (P.cube_gather, a launch over all bricks) the
+  // id follows from the brick's Morton coordinates: the value the host found in cell_vnodes for every cell, so the
+  // value loads below do not wait for an index load. Else: from the index array of the cell that holds the node
+  const bool lattice = P.cube_gather != 0 && subset == nullptr && P.brick_cell0 == nullptr;
+  const int lat_nx = 4 * P.cube_nb1 + 1;  // lattice nodes per direction
+  auto brick_node = [&](int b, int X, int Y, int Z) -> int {
+    if (lattice) {
+      const unsigned bk = (unsigned)b;
+      return (4 * morton_compact3(bk) + X) + lat_nx * ((4 * morton_compact3(bk >> 1) + Y) + lat_nx * (4 * morton_compact3(bk >> 2) + Z));
+    }
+    const int cx = min(X / 2, 1), cy = min(Y / 2, 1), cz = min(Z / 2, 1);
+    const int a = (X - 2 * cx) + 3 * ((Y - 2 * cy) + 3 * (Z - 2 * cz));
+    return P.cell_vnodes[(cell0(b) + cx + 2 * cy + 4 * cz) * 27 + a];
+  };
 
   if (tid < 48) {
     const int mat = tid >> 4, r = (tid >> 2) & 3, cc = tid & 3;
@@ -178,7 +192,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
                       C::WAVES * C::CPW * CS >= 2 * C::BPG * 4 * BN3 && C::CPG * C::OC >= 2 * C::BPG * 4 * (45 + 75),
                   "prolongation scratch in LDS");
     static_assert(C::BPG * BN3 <= 2 * C::THREADS, "two brick nodes per thread");
-    // the gather's loads (node id, then x and the mask) are issued first: they are in flight while the stages run
+    // the gather's loads (x and the mask, behind the node id's where it is loaded) are issued first: they are in
+    // flight while the stages run
     int gn[2];
     unsigned gm[2];
     double gx[2][4];
@@ -188,9 +203,7 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
       gn[it] = -1;
       if (bi < nbg) {
         const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
-        const int cx = min(X / 2, 1), cy = min(Y / 2, 1), cz = min(Z / 2, 1);
-        const int a = (X - 2 * cx) + 3 * ((Y - 2 * cy) + 3 * (Z - 2 * cz));
-        const int node = P.cell_vnodes[(cell0(brick_of(bi)) + cx + 2 * cy + 4 * cz) * 27 + a];
+        const int node = brick_node(brick_of(bi), X, Y, Z);
         gn[it] = node;
         gx[it][0] = P.v[(int64_t)node * 3];
         gx[it][1] = P.v[(int64_t)node * 3 + 1];
@@ -267,48 +280,81 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     }
   }
   // ---------------- gather the group's brick nodes: v (masked: P v) or u, p, H, and the node ids (PRO: done above)
-  for (int t = tid; t < (PRO ? 0 : C::BPG * BN3); t += C::THREADS) {
-    const int bi = t / BN3, n = t % BN3;
-    if (bi >= nbg) break;
-    const int brick = brick_of(bi);
-    const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
-    const int cx = min(X / 2, 1), cy = min(Y / 2, 1), cz = min(Z / 2, 1);
-    const int a = (X - 2 * cx) + 3 * ((Y - 2 * cy) + 3 * (Z - 2 * cz));
-    const int node = P.cell_vnodes[(cell0(brick) + cx + 2 * cy + 4 * cz) * 27 + a];
-    const int64_t i3 = (int64_t)node * 3;
-    Real *b = sB + bi * NF * FB + X + SY * Y + SZ * Z;
-    if constexpr (ST) {
-      double h[3] = {0., 0., 0.};
+  // Two brick nodes per thread; the value loads of both are issued before the first LDS store
+  if constexpr (!PRO) {
+    static_assert(C::BPG * BN3 <= 2 * C::THREADS, "two brick nodes per thread");
+    constexpr int NG = ST ? 13 : 8;  // ST: u (3), p, h1, h2, h3 (3 each); J.v: v (3), v_p, or rb and jd (4 each) with jx0
+    int gn[2];
+    unsigned gm[2] = {0u, 0u};
+    double gv[2][NG];
 #pragma unroll
-      for (int cc = 0; cc < 3; ++cc) {
-        if (P.n_hist > 0) h[cc] += P.alpha[1] * P.h1[i3 + cc];
-        if (P.n_hist > 1) h[cc] += P.alpha[2] * P.h2[i3 + cc];
-        if (P.n_hist > 2) h[cc] += P.alpha[3] * P.h3[i3 + cc];
+    for (int it = 0; it < 2; ++it) {
+      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi;
+      gn[it] = -1;
+      if (bi < nbg) {
+        const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
+        const int node = brick_node(brick_of(bi), X, Y, Z);
+        const int64_t i3 = (int64_t)node * 3;
+        gn[it] = node;
+        if constexpr (ST) {
+          gv[it][0] = P.u[i3], gv[it][1] = P.u[i3 + 1], gv[it][2] = P.u[i3 + 2], gv[it][3] = P.u[voff + node];
+#pragma unroll
+          for (int cc = 0; cc < 3; ++cc) {
+            if (P.n_hist > 0) gv[it][4 + cc] = P.h1[i3 + cc];
+            if (P.n_hist > 1) gv[it][7 + cc] = P.h2[i3 + cc];
+            if (P.n_hist > 2) gv[it][10 + cc] = P.h3[i3 + cc];
+          }
+        } else {
+          if (P.jx0) {
+            gv[it][0] = P.rb[i3], gv[it][1] = P.rb[i3 + 1], gv[it][2] = P.rb[i3 + 2], gv[it][3] = P.rb[voff + node];
+            gv[it][4] = P.jd[i3], gv[it][5] = P.jd[i3 + 1], gv[it][6] = P.jd[i3 + 2], gv[it][7] = P.jd[voff + node];
+          } else {
+            gv[it][0] = P.v[i3], gv[it][1] = P.v[i3 + 1], gv[it][2] = P.v[i3 + 2], gv[it][3] = P.v[voff + node];
+          }
+          gm[it] = P.vmask ? P.vmask[node] : 0u;
+        }
       }
-      b[0] = (Real)P.u[i3];
-      b[FB] = (Real)P.u[i3 + 1];
-      b[2 * FB] = (Real)P.u[i3 + 2];
-      b[3 * FB] = (Real)P.u[voff + node];
-      b[4 * FB] = (Real)h[0];
-      b[5 * FB] = (Real)h[1];
-      b[6 * FB] = (Real)h[2];
-    } else {
-      double v0, v1, v2, vp;
-      if (P.jx0) {  // the first Jacobi sweep from 0: v = 0 + omega b / d (mg_jacobi_update's arithmetic)
-        v0 = 0.0 + P.jomega * P.rb[i3] / P.jd[i3];
-        v1 = 0.0 + P.jomega * P.rb[i3 + 1] / P.jd[i3 + 1];
-        v2 = 0.0 + P.jomega * P.rb[i3 + 2] / P.jd[i3 + 2];
-        vp = 0.0 + P.jomega * P.rb[voff + node] / P.jd[voff + node];
-      } else {
-        v0 = P.v[i3], v1 = P.v[i3 + 1], v2 = P.v[i3 + 2], vp = P.v[voff + node];
-      }
-      const unsigned m = P.vmask ? P.vmask[node] : 0u;
-      b[0] = (m & 1u) ? Real(0) : (Real)v0;
-      b[FB] = (m & 2u) ? Real(0) : (Real)v1;
-      b[2 * FB] = (m & 4u) ? Real(0) : (Real)v2;
-      b[3 * FB] = (Real)vp;
     }
-    sNode[bi * BN3P + n] = node;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      if (gn[it] < 0) continue;
+      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi;
+      const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
+      const double (&g)[NG] = gv[it];
+      Real *b = sB + bi * NF * FB + X + SY * Y + SZ * Z;
+      if constexpr (ST) {
+        double h[3] = {0., 0., 0.};
+#pragma unroll
+        for (int cc = 0; cc < 3; ++cc) {
+          if (P.n_hist > 0) h[cc] += P.alpha[1] * g[4 + cc];
+          if (P.n_hist > 1) h[cc] += P.alpha[2] * g[7 + cc];
+          if (P.n_hist > 2) h[cc] += P.alpha[3] * g[10 + cc];
+        }
+        b[0] = (Real)g[0];
+        b[FB] = (Real)g[1];
+        b[2 * FB] = (Real)g[2];
+        b[3 * FB] = (Real)g[3];
+        b[4 * FB] = (Real)h[0];
+        b[5 * FB] = (Real)h[1];
+        b[6 * FB] = (Real)h[2];
+      } else {
+        double v0, v1, v2, vp;
+        if (P.jx0) {  // the first Jacobi sweep from 0: v = 0 + omega b / d (mg_jacobi_update's arithmetic)
+          v0 = 0.0 + P.jomega * g[0] / g[4];
+          v1 = 0.0 + P.jomega * g[1] / g[5];
+          v2 = 0.0 + P.jomega * g[2] / g[6];
+          vp = 0.0 + P.jomega * g[3] / g[7];
+        } else {
+          v0 = g[0], v1 = g[1], v2 = g[2], vp = g[3];
+        }
+        const unsigned m = gm[it];
+        b[0] = (m & 1u) ? Real(0) : (Real)v0;
+        b[FB] = (m & 2u) ? Real(0) : (Real)v1;
+        b[2 * FB] = (m & 4u) ? Real(0) : (Real)v2;
+        b[3 * FB] = (Real)vp;
+      }
+      sNode[bi * BN3P + n] = gn[it];
+    }
   }
   __syncthreads();
 
@@ -983,8 +1029,23 @@ bool pencil_enabled() {  // read per launch: tests compare both kernels in one p
   return !(e && std::atoi(e) == 0);
 }
 
+// The lattice gather (OpParams::cube_gather): on by default on the verified hyper_cube for a launch over all of its
+// bricks; GLS_CUBE_GATHER=0 keeps the index-array gather (A/B, tests)
+bool cube_gather_enabled() {  // read per launch: tests compare both gathers in one process
+  const char *e = std::getenv("GLS_CUBE_GATHER");
+  return !(e && std::atoi(e) == 0);
+}
+static OpParams with_cube_gather(const OpParams &P) {
+  OpParams Q = P;
+  const int64_t nb = P.cube_nb1;
+  Q.cube_gather = nb > 0 && nb <= 1024 && nb * nb * nb * 8 == P.n_cells && (4 * nb + 1) * (4 * nb + 1) * (4 * nb + 1) == P.n_vnodes &&
+                  !P.subset && !P.brick_cell0 && !P.bricks && cube_gather_enabled();
+  return Q;
+}
+
 template <typename Real, int MODE, bool FB = false>
-hipError_t launch_pencil_t(const OpParams &P, const Tables1D &T, hipStream_t s) {
+hipError_t launch_pencil_t(const OpParams &P0, const Tables1D &T, hipStream_t s) {
+  const OpParams P = with_cube_gather(P0);
   const bool gen = P.srf || (MODE != MODE_JVQ && P.force_q);
   const int n_items = ((std::is_same<Real, double>::value || P.brick_cell0) && P.subset) ? P.subset_n : P.n_cells / 8;
   if (n_items <= 0) return hipSuccess;
@@ -1025,7 +1086,8 @@ hipError_t launch_pencil_jv(const OpParams &P, const Tables1D &T, hipStream_t s,
 }
 // y-less residual of the V-cycle, restricted per brick: rb - A v as coarse element vectors [brick][27][4] in
 // P.slab (P.cube_nb1 bricks per direction, Morton order); P.jx0 as in launch_pencil_jv; no SRF terms
-hipError_t launch_pencil_jv_restrict(const OpParams &P, const Tables1D &T, hipStream_t s) {
+hipError_t launch_pencil_jv_restrict(const OpParams &P0, const Tables1D &T, hipStream_t s) {
+  const OpParams P = with_cube_gather(P0);
   if (P.n_probe > 0 || P.bricks || P.subset || P.brick_cell0 || P.srf || !P.slab || !P.rb || !P.qdf || P.jx || (P.jx0 && !P.jd) ||
       P.cube_nb1 <= 0 || (int64_t)P.cube_nb1 * P.cube_nb1 * P.cube_nb1 * 8 != P.n_cells)
     return hipErrorNotSupported;
@@ -1051,7 +1113,8 @@ hipError_t launch_pencil_jv_restrict(const OpParams &P, const Tables1D &T, hipSt
 // fused damped-Jacobi sweep from x + P xc (P.jx = P.v = x, P.pxc = xc on the next-coarser nested level of
 // P.cube_nb1 cells per direction): brick-interior nodes are stored here, brick-surface nodes by
 // brick_slab_sum_cube from their x + P xc in P.pxp; no SRF terms
-hipError_t launch_pencil_jv_prolong(const OpParams &P, const Tables1D &T, hipStream_t s) {
+hipError_t launch_pencil_jv_prolong(const OpParams &P0, const Tables1D &T, hipStream_t s) {
+  const OpParams P = with_cube_gather(P0);
   if (P.n_probe > 0 || P.bricks || P.subset || P.brick_cell0 || P.srf || !(P.slab || P.slabf) || !P.qdf || !P.pxc || !P.pxp || P.pxp == P.jx || !P.jx ||
       P.jx != P.v || !P.jb || !P.jd || P.rb || P.jx0 || P.ev || P.cube_nb1 <= 0 || P.cube_nb1 > 1023 ||
       (int64_t)P.cube_nb1 * P.cube_nb1 * P.cube_nb1 * 8 != P.n_cells)

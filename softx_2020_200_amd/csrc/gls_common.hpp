@@ -117,8 +117,14 @@ struct OpParams {
   // with the same code)
   double *cq;
   int cq_mode;
-  int cube_nb1;               // pencil J.v with the in-kernel restriction / prolongation: bricks per direction of
-                              //   the hyper_cube (= cells per direction of the next-coarser nested level)
+  int cube_nb1;               // > 0: the verified structured hyper_cube (gls_ctx::cube_nb1), bricks per direction
+                              //   (= cells per direction of the next-coarser nested level: the pencil J.v with the
+                              //   in-kernel restriction / prolongation); 0: a general mesh
+  // pencil kernels, set by their launchers (cube_nb1 > 0, Q2, a launch over all bricks, GLS_CUBE_GATHER not 0): the
+  // gather computes brick b's node (X, Y, Z) as (4 bx + X) + NX ((4 by + Y) + NX (4 bz + Z)), NX = 4 cube_nb1 + 1,
+  // (bx, by, bz) = b's Morton coordinates, instead of loading it from cell_vnodes (the identity the host verified
+  // cell by cell); 0: the index arrays
+  int cube_gather;
   // with jx (FP32 pencil J.v on the cube, hyper_cube slab sum): the V-cycle's coarse correction prolongated in
   // front of the fused damped-Jacobi sweep: the sweep starts from xp = jx + P pxc, formed in the gather. pxc: the
   // next-coarser level's vector, lexicographic lattice of 2 cube_nb1 + 1 nodes. Brick-interior nodes store their

@@ -99,7 +99,8 @@ struct gls_ctx {
   DevBuf<double> slab2;  // the fused residual + linearization pass: the residual's brick-surface slab
   DevBuf<int32_t> sum_nodes, sum_off, sum_slots;
   int cube_nb1 = 0;  // > 0: the mesh is the structured hyper_cube with cube_nb1 bricks per direction
-                     // (k_slab_sum_cube computes the slab slots from the lattice; GLS_SLAB_CSR=1: off)
+                     // (k_slab_sum_cube computes the slab slots from the lattice, the Q2 pencil kernels their
+                     // brick nodes' ids, OpParams::cube_gather; GLS_SLAB_CSR=1: off)
   // colored brick launches (opt-in GLS_BRICK_COLORS=1): bricks greedily colored in Morton order so
   // that no two bricks of a color share a node (the 2x2x2 parity classes on a brick lattice: 8
   // colors); surface-node sums carried across colors in acc, no slab and no k_slab_sum. Measured

@@ -41,6 +41,7 @@ hipError_t launch_pencil_lin(const OpParams &P, const Tables1D &T, hipStream_t s
 hipError_t launch_pencil_reslin(const OpParams &P, const Tables1D &T, hipStream_t s);
 hipError_t launch_pencil_ev(int mode, const OpParams &P, const Tables1D &T, hipStream_t s, bool f32 = false);  // forest sibling-group bricks -> element vectors
 bool pencil_enabled();
+bool cube_gather_enabled();  // GLS_CUBE_GATHER (read per launch): the pencil kernels' lattice gather, OpParams::cube_gather
 // persistent wave-per-brick versions (gls_brick_wave.hip), selected by the launchers above
 hipError_t launch_brick_wave(int k, int mode, const OpParams &P, const Tables1D &T, hipStream_t s);
 hipError_t launch_brick_wave_jv_f32(int k, const OpParams &P, const Tables1D &T, hipStream_t s);

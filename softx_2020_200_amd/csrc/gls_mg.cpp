@@ -414,7 +414,7 @@ std::vector<unsigned char> coarse_graph_key(gls_ctx *g, const double *b, const d
                                                    int pre, double om) {
   const gls::OpParams P = make_params(g);
   const void *ptrs[7] = {b, x, y, g->diag.p, g->qdata.p, g->qdata32.p, brick_slab(g)};
-  const int64_t ints[4] = {pre, g->n_dofs, (int64_t)g->smooth_f32, (int64_t)slab_f32()};
+  const int64_t ints[5] = {pre, g->n_dofs, (int64_t)g->smooth_f32, (int64_t)slab_f32(), (int64_t)gls::cube_gather_enabled()};
   std::vector<unsigned char> k(sizeof(P) + sizeof(ptrs) + sizeof(ints) + sizeof(om));
   unsigned char *o = k.data();
   std::memcpy(o, &P, sizeof(P));
