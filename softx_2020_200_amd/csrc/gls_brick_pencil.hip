@@ -21,6 +21,14 @@
 // sums per brick node). The linearization is read from the pencil layout (qdp_base) that MODE_LIN
 // writes: per (qz, value) one contiguous row of 54 entries per wave.
 //
+// Index bookkeeping ("Pencil bookkeeping"): the FP32 launches sit at the VALU issue limit, so the integers
+// are kept off the vector unit where they can be. What depends on the brick only (its Morton coordinates, the lattice
+// id of its node 0, its place in the linearization's layout, the owner-rule flags of RST / PRO) is formed once per
+// workgroup on the scalar unit and selected per lane by the lane's brick; a thread's two brick nodes
+// t -> (brick, n, X, Y, Z) come from brick_node_idx (24-bit multiplies and shifts) in the gather and again in the
+// epilogue, which maps nodes to threads the same way; node (X, Y, Z) sits at n in the brick arrays. The Oseen J.v
+// without the SRF term runs no value-only passes of v: component cc's velocity sweep already holds v_cc.
+//
 // The pointwise algebra restates gls_navier_stokes.cc:548-622 (the Jacobian's action, SURVEY.md
 // Appendix A) with the same operation order per term as gls_brick_kernels.hip MODE_JVQ.
 #include "gls_brick_common.hpp"
@@ -138,23 +146,45 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   const int n_groups = (n_items + 2) / 3;
   const int g = xcd_swizzle((int)blockIdx.x, n_groups);      // XCD-aware: contiguous Morton triples per XCD
   const int nbg = min(3, n_items - 3 * g);                   // bricks in this group (last one may be short)
-  auto brick_of = [&](int bi) { return subset ? subset[3 * g + bi] : 3 * g + bi; };
   // first cell of a brick: 8 b on the cube; the listed cell on an adapted forest's sibling groups
   auto cell0 = [&](int b) -> int64_t { return P.brick_cell0 ? (int64_t)P.brick_cell0[b] : (int64_t)b * 8; };
   const int64_t voff = (int64_t)3 * P.n_vnodes;
-  // node (X, Y, Z) of brick b's 5^3 lattice. On the verified hyper_cube (P.cube_gather, a launch over all bricks) the
-  // id follows from the brick's Morton coordinates: the value the host found in cell_vnodes for every cell, so the
-  // value loads below do not wait for an index load. Else: from the index array of the cell that holds the node
+  // On the verified hyper_cube (P.cube_gather, a launch over all bricks) a brick node's id follows from the brick's
+  // Morton coordinates: the value the host found in cell_vnodes for every cell, so the value loads below do not wait
+  // for an index load. Else: from the index array of the cell that holds the node
   const bool lattice = P.cube_gather != 0 && subset == nullptr && P.brick_cell0 == nullptr;
   const int lat_nx = 4 * P.cube_nb1 + 1;  // lattice nodes per direction
-  auto brick_node = [&](int b, int X, int Y, int Z) -> int {
-    if (lattice) {
-      const unsigned bk = (unsigned)b;
-      return (4 * morton_compact3(bk) + X) + lat_nx * ((4 * morton_compact3(bk >> 1) + Y) + lat_nx * (4 * morton_compact3(bk >> 2) + Z));
-    }
+  auto brick_of = [&](int bi) { return subset ? subset[3 * g + bi] : 3 * g + bi; };
+  // ---------------- the group's bricks: what depends on the brick only is formed here once, from blockIdx, on the
+  // scalar unit; the lanes select by their brick bi (sel3). gbx / gby / gbz: the brick's Morton coordinates on the
+  // cube (a short group's missing bricks: the first one's); gnode0: its lattice node (0, 0, 0); gtri / gb3: its triple
+  // and place in it in the linearization's pencil layout (qdp_base); gtop: bit 3 bi + a set where brick bi is the
+  // domain's last along axis a (the owner rule of RST / PRO). All but gtop are dead once the gather is done: the FP64
+  // kernels have no scalar register to spare across the sweeps (the 1D tables fill them)
+  int gbx[3], gby[3], gbz[3], gnode0[3], gtri[3], gb3[3], gtop = 0;
+#pragma unroll
+  for (int b3 = 0; b3 < 3; ++b3) {
+    const int i = 3 * g + (b3 < nbg ? b3 : 0);
+    const unsigned bk = (unsigned)__builtin_amdgcn_readfirstlane(subset ? subset[i] : i);
+    const int top = P.cube_nb1 - 1;
+    gtri[b3] = (int)(bk / 3u), gb3[b3] = (int)(bk - 3u * (bk / 3u));
+    gbx[b3] = morton_compact3(bk), gby[b3] = morton_compact3(bk >> 1), gbz[b3] = morton_compact3(bk >> 2);
+    gnode0[b3] = 4 * gbx[b3] + lat_nx * (4 * gby[b3] + lat_nx * (4 * gbz[b3]));
+    if (RST || PRO) gtop |= ((gbx[b3] == top ? 1 : 0) | (gby[b3] == top ? 2 : 0) | (gbz[b3] == top ? 4 : 0)) << (3 * b3);
+  }
+  // id of brick bi's node (X, Y, Z)
+  auto brick_node = [&](int bi, int X, int Y, int Z) -> int {
+    if (lattice)  // = (4 bx + X) + lat_nx ((4 by + Y) + lat_nx (4 bz + Z)); lat_nx <= 4097: 24-bit multiplies
+      return sel3(gnode0, bi) + (int)(__umul24((unsigned)lat_nx, __umul24((unsigned)lat_nx, (unsigned)Z) + (unsigned)Y) + (unsigned)X);
     const int cx = min(X / 2, 1), cy = min(Y / 2, 1), cz = min(Z / 2, 1);
     const int a = (X - 2 * cx) + 3 * ((Y - 2 * cy) + 3 * (Z - 2 * cz));
-    return P.cell_vnodes[(cell0(b) + cx + 2 * cy + 4 * cz) * 27 + a];
+    return P.cell_vnodes[(cell0(brick_of(bi)) + cx + 2 * cy + 4 * cz) * 27 + a];
+  };
+  // the owner rule: a node on a face shared by two bricks belongs to the upper one (local coordinate 0); the domain's
+  // upper faces to their only brick
+  auto owns = [&](int bi, int X, int Y, int Z) -> bool {
+    const int tm = gtop >> (3 * bi);
+    return (X < C::BN - 1 || (tm & 1)) && (Y < C::BN - 1 || (tm & 2)) && (Z < C::BN - 1 || (tm & 4));
   };
 
   if (tid < 48) {
@@ -165,12 +195,14 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   }
   // ---------------- per lane: cell c of this wave, (a, b) position in the cell's 3 x 3 pencil grid
   const bool act = lane < 9 * C::CPW;
-  const int c = act ? lane / 9 : 0, rr = act ? lane % 9 : 0, pa = rr % 3, pb = rr / 3;
+  const int c = act ? div_small<9, 57, 9, 64>(lane) : 0, rr = act ? lane - 9 * c : 0, pb = div_small<3, 11, 5, 16>(rr), pa = rr - 3 * pb;
   const int cw = wave * C::CPW + c, bi = cw >> 3, ci = cw & 7;
   const bool valid = act && bi < nbg;
   const int brick = brick_of(valid ? bi : 0);
   const int cx = ci & 1, cy = (ci >> 1) & 1, cz = ci >> 2;
   const int64_t gcell = cell0(brick) + (valid ? ci : 0);
+  // the lane's rows of the linearization (pencil layout): qdp_base(brick, ci, pa + 3 pb)
+  const int64_t lane_qdp = qdp_base_lane(sel3(gtri, valid ? bi : 0), sel3(gb3, valid ? bi : 0), valid ? ci : 0, pa, pb);
   const Real hx = (Real)P.geo[gcell * 4 + 0], hy = (Real)P.geo[gcell * 4 + 1], hz = (Real)P.geo[gcell * 4 + 2];
   const Real ihx = Real(1) / hx, ihy = Real(1) / hy, ihz = Real(1) / hz;
   const Real wxx = ihx * ihx, wyy = ihy * ihy, wzz = ihz * ihz;
@@ -180,7 +212,7 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   if constexpr (!ST) {
     const Real *base = std::is_same<Real, double>::value ? reinterpret_cast<const Real *>(P.qd)
                                                           : reinterpret_cast<const Real *>(P.qdf);
-    qrow = base + qdp_base(brick, valid ? ci : 0, pa + 3 * pb);
+    qrow = base + lane_qdp;
   }
   // ---------------- PRO: P xc at the nodes of the group's bricks, line by line (q2_prolong_line) along x, y, z. FP64
   // in LDS areas that are not live yet: the x stage [brick][field][j + 3 k][X] and the y stage [brick][field][k][Y][X]
@@ -199,11 +231,10 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     double gx[2][4];
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
-      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi;
+      const BrickNodeIdx q = brick_node_idx(tid + it * C::THREADS);
       gn[it] = -1;
-      if (bi < nbg) {
-        const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
-        const int node = brick_node(brick_of(bi), X, Y, Z);
+      if (q.bi < nbg) {
+        const int node = brick_node(q.bi, q.X, q.Y, q.Z);
         gn[it] = node;
         gx[it][0] = P.v[(int64_t)node * 3];
         gx[it][1] = P.v[(int64_t)node * 3 + 1];
@@ -216,10 +247,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     double o[5];
     // x: one thread per (brick, field, coarse line j, k), its three coarse values from the brick's coarse cell
     for (int t = tid; t < nbg * 36; t += C::THREADS) {
-      const int bf = t / 9, jk = t - 9 * bf, bi = bf >> 2, f = bf & 3, j = jk % 3, k = jk / 3;
-      const unsigned bk = (unsigned)brick_of(bi);
-      const int64_t cn = 2 * morton_compact3(bk) +
-                         (int64_t)ncx * ((2 * morton_compact3(bk >> 1) + j) + (int64_t)ncx * (2 * morton_compact3(bk >> 2) + k));
+      const int bf = div_small<9, 57, 9, 128>(t), jk = t - 9 * bf, bi = bf >> 2, f = bf & 3, k = div_small<3, 11, 5, 16>(jk), j = jk - 3 * k;
+      const int64_t cn = 2 * sel3(gbx, bi) + (int64_t)ncx * ((2 * sel3(gby, bi) + j) + (int64_t)ncx * (2 * sel3(gbz, bi) + k));
       const double *c = f < 3 ? P.pxc + cn * 3 + f : P.pxc + (int64_t)3 * ncx * ncx * ncx + cn;
       const int st = f < 3 ? 3 : 1;
       q2_prolong_line(c[0], c[st], c[2 * st], o);
@@ -229,7 +258,7 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     __syncthreads();
     // y: one thread per (brick, field, k, X)
     for (int t = tid; t < nbg * 60; t += C::THREADS) {
-      const int bf = t / 15, r = t - 15 * bf, k = r / 5, X = r - 5 * k;
+      const int bf = div_small<15, 274, 12, 256>(t), r = t - 15 * bf, k = div_small<5, 52, 8, 32>(r), X = r - 5 * k;
       const double *x = dPX + bf * 45 + 15 * k + X;
       q2_prolong_line(x[0], x[5], x[10], o);
 #pragma unroll
@@ -238,7 +267,7 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     __syncthreads();
     // z: one thread per (brick, field, Y, X)
     for (int t = tid; t < nbg * 100; t += C::THREADS) {
-      const int bf = t / 25, yx = t - 25 * bf;
+      const int bf = div_small<25, 2622, 16, 512>(t), yx = t - 25 * bf;
       const double *y = dPY + bf * 75 + yx;
       q2_prolong_line(y[0], y[25], y[50], o);
 #pragma unroll
@@ -249,8 +278,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       if (gn[it] < 0) continue;
-      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi, node = gn[it];
-      const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
+      const BrickNodeIdx q = brick_node_idx(tid + it * C::THREADS);
+      const int bi = q.bi, n = q.n, X = q.X, Y = q.Y, Z = q.Z, node = gn[it];
       const double *pz = dPZ + bi * 4 * BN3 + n;
       const double v0 = gx[it][0] + pz[0], v1 = gx[it][1] + pz[BN3], v2 = gx[it][2] + pz[2 * BN3], vp = gx[it][3] + pz[3 * BN3];
       if (GLS_PENCIL_PRO_XP_LDS && X > 0 && X < BN - 1 && Y > 0 && Y < BN - 1 && Z > 0 && Z < BN - 1) {  // kept for the node's update
@@ -261,17 +290,15 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
       } else {
         // a brick-surface node: x keeps its old value (the other bricks holding the node gather it in this
         // launch); the one brick that owns the node (restrict_store's rule) hands xp to the slab sum in P.pxp
-        const unsigned bk = (unsigned)brick_of(bi);
-        const int top = P.cube_nb1 - 1;
-        if ((X < BN - 1 || morton_compact3(bk) == top) && (Y < BN - 1 || morton_compact3(bk >> 1) == top) &&
-            (Z < BN - 1 || morton_compact3(bk >> 2) == top)) {
+        if (owns(bi, X, Y, Z)) {
           P.pxp[(int64_t)node * 3] = v0;
           P.pxp[(int64_t)node * 3 + 1] = v1;
           P.pxp[(int64_t)node * 3 + 2] = v2;
           P.pxp[voff + node] = vp;
         }
       }
-      Real *b = sB + bi * NF * FB + X + SY * Y + SZ * Z;
+      static_assert(SY == BN && SZ == BN * BN, "brick arrays: node (X, Y, Z) at its lattice index n");
+      Real *b = sB + bi * NF * FB + n;
       b[0] = (gm[it] & 1u) ? Real(0) : (Real)v0;
       b[FB] = (gm[it] & 2u) ? Real(0) : (Real)v1;
       b[2 * FB] = (gm[it] & 4u) ? Real(0) : (Real)v2;
@@ -289,11 +316,10 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     double gv[2][NG];
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
-      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi;
+      const BrickNodeIdx q = brick_node_idx(tid + it * C::THREADS);
       gn[it] = -1;
-      if (bi < nbg) {
-        const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
-        const int node = brick_node(brick_of(bi), X, Y, Z);
+      if (q.bi < nbg) {
+        const int node = brick_node(q.bi, q.X, q.Y, q.Z);
         const int64_t i3 = (int64_t)node * 3;
         gn[it] = node;
         if constexpr (ST) {
@@ -318,10 +344,11 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       if (gn[it] < 0) continue;
-      const int t = tid + it * C::THREADS, bi = t / BN3, n = t - BN3 * bi;
-      const int X = n % BN, Y = (n / BN) % BN, Z = n / (BN * BN);
+      const BrickNodeIdx q = brick_node_idx(tid + it * C::THREADS);
+      const int bi = q.bi, n = q.n;
       const double (&g)[NG] = gv[it];
-      Real *b = sB + bi * NF * FB + X + SY * Y + SZ * Z;
+      static_assert(SY == BN && SZ == BN * BN, "brick arrays: node (X, Y, Z) at its lattice index n");
+      Real *b = sB + bi * NF * FB + n;
       if constexpr (ST) {
         double h[3] = {0., 0., 0.};
 #pragma unroll
@@ -489,11 +516,11 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   // ---------------- brick reduction (fixed cell order per node) + scatter: one thread per brick node;
   // fused: the launch's damped-Jacobi / residual-form / FP32-slab options apply
   auto reduce_scatter = [&](double *yo, double *slo, bool fused) {
-    for (int t = tid; t < C::BPG * BN3; t += C::THREADS) {
-      const int rb_ = t / BN3, n = t % BN3;
+    for (int t = tid; t < C::BPG * BN3; t += C::THREADS) {  // the gather's mapping of nodes to threads
+      const BrickNodeIdx q = brick_node_idx(t);
+      const int rb_ = q.bi, n = q.n, Xn = q.X, Yn = q.Y, Zn = q.Z;
       if (rb_ >= nbg) break;
       const int bk = brick_of(rb_);
-      const int Xn = n % BN, Yn = (n / BN) % BN, Zn = n / (BN * BN);
       Real s[4] = {0, 0, 0, 0};
 #pragma unroll
       for (int kz = 0; kz < 2; ++kz) {
@@ -514,7 +541,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
         }
       }
       const int node = sNode[rb_ * BN3P + n];
-      const int64_t gi[4] = {(int64_t)node * 3, (int64_t)node * 3 + 1, (int64_t)node * 3 + 2, voff + node};
+      const int64_t i3 = (int64_t)node * 3;
+      const int64_t gi[4] = {i3, i3 + 1, i3 + 2, voff + node};
       const bool interior = Xn > 0 && Xn < BN - 1 && Yn > 0 && Yn < BN - 1 && Zn > 0 && Zn < BN - 1;
       if (interior) {
         if (fused && P.jx) {  // fused damped-Jacobi sweep (interior nodes: no other brick reads this x)
@@ -582,11 +610,10 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     double *const dR = reinterpret_cast<double *>(sB), *const dY = dR + C::BPG * 4 * BN3;
     double *const dX = reinterpret_cast<double *>(sO);
     // r of every brick node (cell sums in reduce_scatter's order)
-    for (int t = tid; t < C::BPG * BN3; t += C::THREADS) {
-      const int rb_ = t / BN3, n = t % BN3;
+    for (int t = tid; t < C::BPG * BN3; t += C::THREADS) {  // the gather's mapping of nodes to threads
+      const BrickNodeIdx q = brick_node_idx(t);
+      const int rb_ = q.bi, n = q.n, Xn = q.X, Yn = q.Y, Zn = q.Z;
       if (rb_ >= nbg) break;
-      const int bk = brick_of(rb_);
-      const int Xn = n % BN, Yn = (n / BN) % BN, Zn = n / (BN * BN);
       Real s[4] = {0, 0, 0, 0};
 #pragma unroll
       for (int kz = 0; kz < 2; ++kz) {
@@ -607,15 +634,12 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
         }
       }
       const int node = sNode[rb_ * BN3P + n];
-      // a node on a face shared by two bricks belongs to the upper one (local coordinate 0); the domain's
-      // upper faces to their only brick
-      const int top = P.cube_nb1 - 1;
-      const bool own = (Xn < BN - 1 || morton_compact3((unsigned)bk) == top) && (Yn < BN - 1 || morton_compact3((unsigned)bk >> 1) == top) &&
-                       (Zn < BN - 1 || morton_compact3((unsigned)bk >> 2) == top);
+      const bool own = owns(rb_, Xn, Yn, Zn);
       const unsigned m = P.vmask ? P.vmask[node] : 0u;  // constrained rows restrict onto constrained coarse rows only: 0
       double r[4] = {-(double)s[0], -(double)s[1], -(double)s[2], -(double)s[3]};
       if (own) {
-        const int64_t gi[4] = {(int64_t)node * 3, (int64_t)node * 3 + 1, (int64_t)node * 3 + 2, voff + node};
+        const int64_t i3 = (int64_t)node * 3;
+        const int64_t gi[4] = {i3, i3 + 1, i3 + 2, voff + node};
 #pragma unroll
         for (int f = 0; f < 4; ++f) r[f] = P.rb[gi[f]] - (double)s[f];
         if (P.jx0) {  // the fused first Jacobi sweep's x (formed in the gather), stored once per node
@@ -629,7 +653,7 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     __syncthreads();
     // x: [brick][field][Y + 5 Z][cx]
     for (int t = tid; t < nbg * 4 * 25; t += C::THREADS) {
-      const int bf = t / 25, yz = t - bf * 25;
+      const int bf = div_small<25, 2622, 16, 512>(t), yz = t - bf * 25;
       const double *r = dR + bf * BN3 + BN * yz;
       double *o = dX + bf * 75 + 3 * yz;
       r53(r[0], r[1], r[2], r[3], r[4], o[0], o[1], o[2]);
@@ -637,7 +661,7 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     __syncthreads();
     // y: [brick][field][cy + 3 Z][cx]
     for (int t = tid; t < nbg * 4 * 15; t += C::THREADS) {
-      const int bf = t / 15, zx = t - bf * 15, Z = zx / 3, cx_ = zx - 3 * Z;
+      const int bf = div_small<15, 274, 12, 256>(t), zx = t - bf * 15, Z = div_small<3, 11, 5, 16>(zx), cx_ = zx - 3 * Z;
       const double *r = dX + bf * 75 + 15 * Z + cx_;
       double *o = dY + bf * 45 + 9 * Z + cx_;
       r53(r[0], r[3], r[6], r[9], r[12], o[0], o[3], o[6]);
@@ -645,7 +669,7 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
     __syncthreads();
     // z: one thread per (brick, cx, cy), its three coarse nodes' four fields as two 16-byte stores each
     for (int t = tid; t < nbg * 9; t += C::THREADS) {
-      const int rb_ = t / 9, xy = t - rb_ * 9;
+      const int rb_ = div_small<9, 57, 9, 32>(t), xy = t - rb_ * 9;
       double cv[4][3];
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
@@ -701,8 +725,8 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
       tauq[qz] = Real(1) / sqrt((Real)P.sdt2 + t1 * t1 + Real(9) * (t2 * t2));
     }
     // MODE_LIN: the lane's linearization rows (pencil layout, qdp_base), FP64 and the FP32 copy
-    double *const lrow = LIN && P.qd ? P.qd + qdp_base(brick, valid ? ci : 0, pa + 3 * pb) : nullptr;
-    float *const lrowf = LIN && P.qdf ? P.qdf + qdp_base(brick, valid ? ci : 0, pa + 3 * pb) : nullptr;
+    double *const lrow = LIN && P.qd ? P.qd + lane_qdp : nullptr;
+    float *const lrowf = LIN && P.qdf ? P.qdf + lane_qdp : nullptr;
     const bool f32_all = !P.oseen;  // the Oseen smoother reads only u (0..2) and tau (12) of the FP32 copy
     auto st_lin = [&](int qz, int v, Real x) {
       if (!valid) return;
@@ -917,15 +941,20 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
   // values of v (all components) and vp, grad vp at the lane's three points: every test field needs
   // them; each velocity component's gradient / Laplacian sweeps run later, next to its test field, so
   // that only one component's Y stage is live at a time
-  Real vq[3][3], vpq[3], gvp[3][3];
+  // The Oseen operator without the SRF term reads v only as alpha_jac v_cc in component cc's own pass, whose velocity
+  // sweep forms the same BB line (the same x and y sweep expressions): no value-only passes there (VALS)
+  constexpr bool VALS = !OS || GEN;
+  Real vq[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, vpq[3], gvp[3][3];
   {
     Real dz[3];
+    if constexpr (VALS) {
 #pragma unroll
-    for (int cc = 0; cc < 3; ++cc) {
-      Real bb[3];
-      forward(cc, 0, bb, dz, dz, dz);
+      for (int cc = 0; cc < 3; ++cc) {
+        Real bb[3];
+        forward(cc, 0, bb, dz, dz, dz);
 #pragma unroll
-      for (int qz = 0; qz < 3; ++qz) vq[cc][qz] = zval(bb, qz);
+        for (int qz = 0; qz < 3; ++qz) vq[cc][qz] = zval(bb, qz);
+      }
     }
     Real pb_[3], pbd[3], pdb[3];
     forward(3, 1, pb_, pbd, pdb, dz);
@@ -954,6 +983,10 @@ __global__ void __launch_bounds__(256, (std::is_same<Real, float>::value ? GLS_P
       }
       if (PIPE && cc < 2) ld_comp(cc + 1);
       forward(cc, 2, Yc[0], Yc[1], Yc[2], Yc[3]);
+      if constexpr (!VALS) {
+#pragma unroll
+        for (int qz = 0; qz < 3; ++qz) vq[cc][qz] = zval(Yc[0], qz);
+      }
     }
     Real Z[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
 #pragma unroll
