@@ -1125,6 +1125,10 @@ struct Solver {
   }
   Solver(Params &p, bool mg) : P(p), use_mg(mg), use_ilu(mg) { timer.on = P.timer != "none"; }
   bool use_ilu;              // assembled ILU(0) where no multigrid hierarchy exists (--precond jacobi: off)
+  // --mg-smoother ilu|jacobi|vanka: the smoother of the hierarchy multigrid (--precond hmg / method = amg); -1: the
+  // default (Q2-Q1 ILU(0), equal order damped Jacobi). --mg-sweeps N: its pre / post sweep count (0: the default).
+  // mg_smoother_used: what the attached hierarchy smooths with (the library refuses some levels: the default then)
+  int mg_smoother = -1, mg_sweeps = 0, mg_smoother_used = -1, mg_sweeps_used = 0;
   int forest_mode = 0;       // adapted meshes: 0 default, 1 --precond ilu (never the hierarchy multigrid),
                              // 2 --precond hmg (the hierarchy multigrid for every method and order)
   gls_ctx *ilu_ctx = nullptr;  // the context the ILU was attached to (a new mesh builds a new context)
@@ -1584,12 +1588,8 @@ struct Solver {
     std::memset(&mp, 0, sizeof(mp));
     mp.n_levels = (int)lv.size();
     mp.levels = lv.data();
-    mp.smoother = P.k != P.kp ? 1 : 0;  // Q2-Q1: ILU(0) sweeps (point Jacobi sees only the PSPG pressure diagonal)
-    mp.pre_smooth = mp.smoother ? 1 : 2;
-    mp.post_smooth = mp.smoother ? 1 : 2;
-    mp.omega = 0.6;
     mp.coarse_direct = 1;
-    ck(gls_mg_attach_transfers(ctx, &mp, po.data(), pc.data(), pw.data(), pi.data()), "gls_mg_attach_transfers");
+    attach_transfers_with_smoother(ctx, mp, po.data(), pc.data(), pw.data(), pi.data(), "gls_mg_attach_transfers");
   }
 
   void setup(int n) {
@@ -1705,6 +1705,32 @@ struct Solver {
     close_lines(ld, lo, lm, lw);
   }
 
+  // the hierarchy's smoother and sweeps: the default, or --mg-smoother / --mg-sweeps; *fallback: the default again
+  void mg_smoother_params(gls_mg_params &mp, bool fallback) {
+    const int def = P.k != P.kp ? 1 : 0;  // Q2-Q1: ILU(0) sweeps (point Jacobi sees only the PSPG pressure diagonal)
+    mp.smoother = mg_smoother >= 0 && !fallback ? mg_smoother : def;
+    const int sw = mg_sweeps > 0 ? mg_sweeps : (mp.smoother ? 1 : 2);
+    mp.pre_smooth = mp.post_smooth = sw;
+    mp.omega = mp.smoother == 3 ? 0.8 : 0.6;
+    mg_smoother_used = mp.smoother;
+    mg_sweeps_used = sw;
+  }
+  // gls_mg_attach_transfers with the requested smoother; where the library refuses it (GLS_EINVAL: a level with
+  // hanging or slip lines under the cell-Vanka smoother, ...) the present choice, said on stderr
+  void attach_transfers_with_smoother(gls_ctx *c, gls_mg_params mp, const int64_t *const *po, const int32_t *const *pc,
+                                      const double *const *pw, const int64_t *const *pi, const char *what) {
+    mg_smoother_params(mp, false);
+    int rc = gls_mg_attach_transfers(c, &mp, po, pc, pw, pi);
+    if (rc == GLS_EINVAL && mg_smoother >= 0) {
+      if (rank == 0)
+        std::fprintf(stderr, "--mg-smoother %s refused (%s): falling back to the default smoother\n",
+                     mg_smoother == 3 ? "vanka" : mg_smoother == 1 ? "ilu" : "jacobi", gls_last_error());
+      mg_smoother_params(mp, true);
+      rc = gls_mg_attach_transfers(c, &mp, po, pc, pw, pi);
+    }
+    ck(rc, what);
+  }
+
   // Geometric multigrid on the triangulation's refinement hierarchy (gls_mg_attach_transfers): levels =
   // the triangulation coarsened one level at a time (gls_umesh_coarsen_to) down to the coarse mesh, each
   // with its FE space, MappingQ geometry, Dirichlet / slip constraints and hanging lines; transfers =
@@ -1802,15 +1828,15 @@ struct Solver {
     std::memset(&mp, 0, sizeof(mp));
     mp.n_levels = (int)lv.size();
     mp.levels = lv.data();
-    mp.smoother = P.k != P.kp ? 1 : 0;  // Q2-Q1: ILU(0) sweeps (point Jacobi sees only the PSPG pressure diagonal)
-    mp.pre_smooth = mp.smoother ? 1 : 2;
-    mp.post_smooth = mp.smoother ? 1 : 2;
-    mp.omega = 0.6;
     mp.coarse_direct = n_coarse <= (plevel_used ? kPLevelDirectMax : 8192) ? 1 : -1;
     if (world == 1) {
-      ck(gls_mg_attach_transfers(ctx, &mp, po.data(), pc.data(), pw.data(), pi.data()), "gls_mg_attach_transfers");
+      attach_transfers_with_smoother(ctx, mp, po.data(), pc.data(), pw.data(), pi.data(), "gls_mg_attach_transfers");
       return;
     }
+    if (mg_smoother == 3 && rank == 0)
+      std::fprintf(stderr, "--mg-smoother vanka refused (the cell-Vanka smoother runs on one rank only): falling back to the "
+                           "default smoother\n");
+    mg_smoother_params(mp, mg_smoother == 3);
     // --np: the fine level is this rank's cells; levels 1..L (whole meshes) run on every rank as one replica
     // hierarchy fed by the all-reduced restriction of the owned rows (gls_mg_attach_replica). P's rows of the
     // rank's local fine DoFs; a level-1 DoF's state comes from the fine DoF it injects, on the rank owning it.
@@ -2169,8 +2195,9 @@ struct Solver {
     const char *krylov = P.lin_method == 1 ? "BiCGStab" : "GMRES";
     char prec[256];
     if (!mg_levels.empty() && (rmesh || space))
-      std::snprintf(prec, sizeof prec, "geometric multigrid %s on the %s refinement hierarchy (%zu levels%s)",
-                    P.k != P.kp ? "V(1,1)-cycle with ILU(0) smoothing" : "V(2,2)-cycle with damped-Jacobi smoothing",
+      std::snprintf(prec, sizeof prec, "geometric multigrid V(%d,%d)-cycle with %s smoothing on the %s refinement hierarchy (%zu levels%s)",
+                    mg_sweeps_used, mg_sweeps_used,
+                    mg_smoother_used == 3 ? "additive cell-Vanka" : mg_smoother_used ? "ILU(0)" : "damped-Jacobi",
                     rmesh ? "forest's" : "triangulation's", mg_levels.size() + 1,
                     plevel_used ? ", the last a Q1-Q1 p-level on the base mesh, dense LU" : "");
     else if (!mg_levels.empty())
@@ -3224,7 +3251,9 @@ int main(int argc, char **argv) {
   // gls_navier_stokes_2d / gls_navier_stokes_3d <file.prm> (applications/gls_navier_stokes_{2d,3d},
   // gls_navier_stokes_3d.cc:22-46): the dimension comes from the program name; the generic
   // binary takes --dim. Extra options: --precond mg|ilu|hmg|jacobi (ilu: never the refinement-hierarchy
-  // multigrid on adapted meshes; hmg: that multigrid for every method and order), --precision N (error table digits),
+  // multigrid on adapted meshes; hmg: that multigrid for every method and order), --mg-smoother ilu|jacobi|vanka and
+  // --mg-sweeps N (the hierarchy multigrid's smoother and its pre / post sweeps; default: ILU(0) V(1,1) on Q2-Q1, damped
+  // Jacobi V(2,2) on equal order), --precision N (error table digits),
   // --stats (solver iteration totals), --ilu-block-dofs N (block-Jacobi ILU subdomains of N DoFs,
   // 0 = one block), --ilu-order cm|multicolor (gls_ilu_set_options), --dump DIR (every iteration's
   // final state for the pipeline tests), --output-eval host|device (the VTU point data from the host vector or,
@@ -3239,6 +3268,7 @@ int main(int argc, char **argv) {
   const char *dump = nullptr;
   int np_ranks = 1;
   int forest_mode = 0;
+  int mg_smoother = -1, mg_sweeps = 0;
   int precision = 4;
   const char *file = nullptr;
   const std::string prog = argv[0];
@@ -3252,6 +3282,17 @@ int main(int argc, char **argv) {
         die("--precond %s: mg, ilu, hmg or jacobi", pc);
       mg = std::strcmp(pc, "jacobi") != 0;
       forest_mode = !std::strcmp(pc, "ilu") ? 1 : !std::strcmp(pc, "hmg") ? 2 : 0;
+    }
+    else if (!std::strcmp(argv[i], "--mg-smoother") && i + 1 < argc) {
+      const char *o = argv[++i];
+      if (!std::strcmp(o, "ilu")) mg_smoother = 1;
+      else if (!std::strcmp(o, "jacobi")) mg_smoother = 0;
+      else if (!std::strcmp(o, "vanka")) mg_smoother = 3;
+      else die("--mg-smoother %s: ilu, jacobi or vanka", o);
+    }
+    else if (!std::strcmp(argv[i], "--mg-sweeps") && i + 1 < argc) {
+      mg_sweeps = std::atoi(argv[++i]);
+      if (mg_sweeps < 1) die("--mg-sweeps must be >= 1");
     }
     else if (!std::strcmp(argv[i], "--precision") && i + 1 < argc) precision = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--stats")) stats = true;
@@ -3315,6 +3356,8 @@ int main(int argc, char **argv) {
   }
   Solver s(P, mg);
   s.forest_mode = forest_mode;
+  s.mg_smoother = mg_smoother;
+  s.mg_sweeps = mg_sweeps;
   s.rank = rank;
   s.world = np_ranks;
   if (np_ranks > 1) {

@@ -200,8 +200,10 @@ typedef struct {
   gls_ctx **levels;
   int pre_smooth, post_smooth, coarse_sweeps;  /* pre: 0 -> 2, < 0 -> none (x = 0, residual = rhs);
                                                   post: < 0 -> 2, 0 -> none; coarse: 0 -> 30 */
-  double omega;                               /* damped-Jacobi weight of the smoother, 0 -> 0.6 */
-  double coarse_omega;                        /* weight of the coarsest-level sweeps, 0 -> omega */
+  double omega;                               /* damped-Jacobi weight of the smoother, 0 -> 0.6
+                                                 (smoother 3: the cell-Vanka damping, 0 -> 0.8) */
+  double coarse_omega;                        /* weight of the coarsest-level Jacobi sweeps, 0 -> omega
+                                                 (smoother 3: 0 -> 0.6 whatever omega is) */
   int coarse_direct;                          /* coarsest level: 0 auto (exact solve when on one GPU
                                                  with <= 2048 DoFs), 1 direct solve (<= 40000 DoFs;
                                                  a gls_mg_attach_replica level <= 8192),
@@ -233,7 +235,17 @@ typedef struct {
                                                  1208-1226); levels with hanging nodes only
                                                  (gls_mg_attach_transfers); 2: ILU(0) on the coarser
                                                  levels, damped Jacobi on the finest (its FP32 brick
-                                                 J.v with mixed_precision) */
+                                                 J.v with mixed_precision); 3: additive cell-Vanka on
+                                                 every level above the coarsest (gls_mg_attach_transfers
+                                                 on one rank; see gls_vanka_sweep): one sweep is
+                                                 x += omega D_m^-1 sum_c R_c^T A_c^-1 R_c (b - A x)
+                                                 with the dense inverse of the assembled Jacobian on
+                                                 each cell's DoFs, averaged by the number of cells
+                                                 holding a DoF; omega 0 -> 0.8. No probed CSR, no
+                                                 colouring; the inverses are rebuilt once per Jacobian
+                                                 state. 3D Q2-Q1 / Q2-Q2 per-cell contexts (mapped or
+                                                 box cells) without hanging / slip lines; else
+                                                 GLS_EINVAL and the context keeps what it had */
   int smoother_operator;                      /* 0: the levels' Newton Jacobian; 1: its Oseen (Picard)
                                                  linearization on the FP32 brick levels (no (grad u) v
                                                  terms, no SUPG tau (v . grad phi) R_s term): cheaper
@@ -262,7 +274,7 @@ int gls_mg_attach_transfers(gls_ctx *ctx, const gls_mg_params *prm, const int64_
  * DoFs, owned and ghost rows; inject (replica n_dofs): the local fine DoF whose value the replica's state
  * takes, on the one rank that owns it (-1 elsewhere). The restriction sums P^T over each rank's owned rows
  * and all-reduces in the replica numbering. prm: pre / post smooth, omega, smoother (0 damped Jacobi, 1
- * ILU(0) per rank = Ifpack additive Schwarz, overlap 0); coarse_direct > 0 with a replica WITHOUT a hierarchy
+ * ILU(0) per rank = Ifpack additive Schwarz, overlap 0; the cell-Vanka smoother 3 is one-rank: GLS_EINVAL); coarse_direct > 0 with a replica WITHOUT a hierarchy
  * of its own (two-level case): the replica level is solved exactly (probed, LU-inverted, <= 8192 DoFs) on
  * every rank; levels / other coarse entries are not used. Host arrays. */
 int gls_mg_attach_replica(gls_ctx *ctx, const gls_mg_params *prm, gls_ctx *replica, const int64_t *p_off,
@@ -311,6 +323,43 @@ int gls_mg_detach(gls_ctx *ctx);
  * data and viscosity follow the hierarchy's (gathered at every Jacobian state). With the replica the
  * N-rank cycle performs the operations of the 1-rank cycle (bench.py --gpus N). */
 int gls_mg_set_coarse_replica(gls_ctx *ctx, gls_ctx *replica, int64_t n_local, const int64_t *local_to_replica);
+/* Additive cell-Vanka smoother (gls_mg_params.smoother = 3) and its building blocks, each callable on a context
+ * without a hierarchy (tests, experiments). Not a reference interface: the reference smooths with Trilinos ML's ILU.
+ * Supported: 3D Q2-Q1 / Q2-Q2 contexts on the per-cell kernels (mapped or box cells), one rank, no hanging-node or
+ * slip lines, no forest context whose sibling groups run the brick (pencil) kernel (gls_forest_bricks > 0), no cell
+ * that holds a node twice (periodic identification across one cell; a periodic mesh in which no cell meets itself is a
+ * conforming mesh to the patches and is supported); anything else returns GLS_EINVAL with the limit named. nd = 81 + (kp+1)^3 DoFs per cell in the element-vector order (velocity
+ * node a, component c at 3 a + c; pressure node b at 81 + b). DEVICE pointers unless said otherwise.
+ *   gls_vanka_sizes            : nd and the padded row length (floats, a multiple of 4) of the FP32 inverses.
+ *   gls_vanka_element_matrices : K [n_cells][nd][nd] row-major, the cells' local Jacobians at the current (or frozen)
+ *                                state, unconstrained: the matrix local_matrix of assembleGLS<true> holds
+ *                                (gls_navier_stokes.cc:519-625), from the J.v linearization cache.
+ *   gls_vanka_patch_inverses   : rebuilds (when the Jacobian's state changed) and copies out A [n_cells][nd][nd], the
+ *                                assembled Jacobian gls_jacobian_apply applies restricted to each cell's DoFs
+ *                                (constrained DoFs: identity rows / columns times D_c), and / or Ainv
+ *                                [n_cells][nd][row floats], its FP32 inverse (FP64 Gauss-Jordan with partial pivoting);
+ *                                either may be NULL. The library keeps A across rebuilds only after a call that asked
+ *                                for it (2 nd^2 doubles per cell; the smoother needs the inverses alone). A singular
+ *                                or non-finite patch: GLS_EINVAL naming the first cell.
+ *   gls_vanka_sweep            : x <- x + omega D_m^-1 sum_c R_c^T A_c^-1 R_c (b - A x) (omega <= 0 -> 0.8); the
+ *                                residual in FP64 by gls_jacobian_apply, the patch products in FP32, sums in a fixed
+ *                                order (bitwise repeatable).
+ *   gls_vanka_detach           : releases the maps, matrices and inverses (gls_mg_detach does it for the levels a
+ *                                hierarchy smoothed).
+ *   gls_vanka_maps             : HOST only, no device: the maps the patches are assembled with. cell_dofs
+ *                                [n_cells][nd]; mult [n_dofs] = cells holding the DoF; nb_off [n_cells + 1] into
+ *                                nb_cell (the cells sharing a DoF with the cell, ascending, itself included) and
+ *                                ov_off [pairs + 1] into (ov_i, ov_j): local indices in the cell / in the neighbour of
+ *                                every shared DoF. Any output may be NULL; call with them NULL for the counts. */
+int gls_vanka_sizes(gls_ctx *ctx, int *nd, int *row_floats);
+int gls_vanka_element_matrices(gls_ctx *ctx, double *K);
+int gls_vanka_patch_inverses(gls_ctx *ctx, double *A, float *Ainv);
+int gls_vanka_sweep(gls_ctx *ctx, double *x, const double *b, double omega);
+int gls_vanka_detach(gls_ctx *ctx);
+int gls_vanka_maps(int dim, int k, int kp, int64_t n_cells, int64_t n_vnodes, int64_t n_pnodes, const int32_t *cell_vnodes,
+                   const int32_t *cell_pnodes, int32_t *cell_dofs, int32_t *mult, int64_t *nb_off, int32_t *nb_cell,
+                   int64_t nb_capacity, int64_t *ov_off, uint8_t *ov_i, uint8_t *ov_j, int64_t ov_capacity,
+                   int64_t *out_pairs, int64_t *out_overlaps);
 /* Assembled ILU(fill) preconditioner for GMRES (replaces setup_ILU, gls_navier_stokes.cc:1161-1176:
  * Trilinos PreconditionILU(ilu_fill, ilu_atol, ilu_rtol, overlap 0) = Ifpack ILU(k), the reference's
  * 'linear solver/method = gmres' with 'ilu preconditioner fill / absolute / relative tolerance',

@@ -927,7 +927,10 @@ int run_cell(gls_ctx *c, int mode, const double *v, double *y) {
     HIP_TRY(gls::vec_csr_condense(y, c->hang.tm.p, c->hang.toff.p, c->hang.tdof.p, c->hang.tw.p,
                                   (int64_t)c->hang.tm.n, c->stream));
   if (!c->probe_local) GLS_TRY(dist_export_add(c, y));
-  if (P.cq_mode == 1) c->cq_valid = true;
+  if (P.cq_mode == 1) {
+    c->cq_valid = true;
+    ++c->cq_epoch;
+  }
   if (lin_diag) {  // the same launch stored the J.v linearization
     c->qd_valid = true;
     c->qd32_valid = P.qdf != nullptr;
@@ -1580,6 +1583,7 @@ int smoother_sweep(gls_ctx *g, double *x, const double *b, double *y, double ome
   if (pxc && ((z && g->ilu.on && !g->ilu.probe_only) || nofuse || !brick || !g->smooth_f32 || g->use_colors || g->cube_nb1 <= 0))
     return set_err(GLS_EINVAL, "fused prolongation not applicable");
   if (z && g->ilu.on && !g->ilu.probe_only) return ilu_sweep(g, x, b, y, z);
+  if (g->vanka.smooth) return vanka_sweep(g, x, b, y, omega);
   if (nofuse || !brick) {
     GLS_TRY(smoother_apply(g, x, y));
     HIP_TRY(gls::mg_jacobi_update(x, b, y, g->diag.p, omega, g->n_dofs, 0, g->stream));

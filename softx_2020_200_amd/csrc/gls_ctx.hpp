@@ -65,6 +65,7 @@ struct gls_ctx {
   // pass and read by the J.v (OpParams::cq); valid with qd_valid's rules
   DevBuf<double> cq;
   bool cq_valid = false;
+  uint64_t cq_epoch = 0;  // counts the diagonal passes that rewrote the cache: what is derived from it (vanka) compares
   DevBuf<float> qdata32;  // FP32 copy of qdata: the multigrid smoother's J.v (mixed precision)
   bool qd32_valid = false;  // stale whenever qdata is recomputed
   bool qd32_partial = false;  // the FP32 copy holds only u and tau (written for the Oseen smoother operator)
@@ -216,6 +217,24 @@ struct gls_ctx {
     }
     ~ILU() { release(); }
   } ilu;
+  // additive cell-Vanka smoother (gls_vanka_host.cpp; gls_mg_params.smoother = 3 and the gls_vanka_* building blocks): the
+  // mesh maps built once on the host, and per Jacobian state the element matrices K, the patch matrices A and their
+  // FP32 inverses
+  struct Vanka {
+    bool on = false;      // maps uploaded
+    bool smooth = false;  // this level's multigrid smoother (set by the attach, cleared by gls_mg_detach)
+    bool valid = false;   // the inverses belong to the cache of epoch `epoch`
+    uint64_t epoch = 0;
+    int nd = 0;
+    DevBuf<int32_t> cell_dofs, nb_cell, flag;
+    DevBuf<int64_t> nb_off, ov_off;
+    DevBuf<uint8_t> ov_i, ov_j, con;  // con [n_dofs]: 1 on the zero_constraints DoFs
+    DevBuf<double> A;     // the patch matrices, kept only once gls_vanka_patch_inverses asked for them (keep_A)
+    bool keep_A = false;
+    DevBuf<double> r;  // gls_vanka_sweep's residual (the V-cycle passes its own scratch)
+    DevBuf<float> Ainv;
+    double setup_s = 0.;  // host wall seconds of the last rebuild (GLS_MG_VERBOSE)
+  } vanka;
   // hanging-node constraints (gls_set_hanging): lines dof <- sum w * master
   struct Hang {
     bool on = false;
@@ -456,6 +475,14 @@ int mg_fine_first_producer(gls_ctx *c, const double **d, double *omega);
 int ilu_probe(gls_ctx *c);
 int ensure_ilu(gls_ctx *c);
 int apply_ilu(gls_ctx *c, const double *v, double *z);
+
+// ---- gls_vanka_host.cpp: the additive cell-Vanka smoother. vanka_refusal: nullptr, or why the context cannot carry it;
+// vanka_attach builds the maps (no-op when on); ensure_vanka rebuilds the inverses when the linearization changed;
+// one sweep x <- x + omega D_m^-1 sum_c R_c^T A_c^-1 R_c (b - A x) (y: scratch; x_zero: x is taken as 0 and set)
+const char *vanka_refusal(const gls_ctx *c);
+int vanka_attach(gls_ctx *c);
+int ensure_vanka(gls_ctx *c);
+int vanka_sweep(gls_ctx *c, double *x, const double *b, double *y, double omega, bool x_zero = false);
 
 // ---- gls_rccl.cpp: the RCCL transport's exchange on a given stream
 int rccl_exchange_on(gls_ctx *c, int phase, hipStream_t stream);

@@ -309,4 +309,23 @@ hipError_t dense_lu_solve_f32(const float *LU, int n, float *x, hipStream_t s, i
 hipError_t mg_jacobi_update(double *x, const double *b, const double *y, const double *d, double omega, int64_t n,
                             int zero_start, hipStream_t s);
 
+// additive cell-Vanka smoother on 3D Q2-Q1 / Q2-Q2 per-cell contexts (gls_vanka.hip). nd = 89 / 108 DoFs per cell;
+// the FP32 inverses are [n_cells][nd][vanka_row_floats(nd)] (rows padded to 16 bytes).
+int vanka_row_floats(int nd);
+// K [n_cells][nd][nd]: the element Jacobians from the linearization cache P.cq (cq_mode 2), unconstrained
+hipError_t launch_vanka_element(int kp, const OpParams &P, const Tables1D &T, double *K, hipStream_t s);
+// A [n_cells][nd][nd]: K summed over each cell's neighbours through the overlap maps (gls_vanka_maps.hpp); DoFs with
+// con[dof] != 0 become rows / columns of the identity times diag[dof]
+hipError_t launch_vanka_patch(int n_cells, int nd, const double *K, const int64_t *nb_off, const int32_t *nb_cell,
+                              const int64_t *ov_off, const uint8_t *ov_i, const uint8_t *ov_j, const int32_t *cell_dofs,
+                              const uint8_t *con, const double *diag, double *A, hipStream_t s);
+// Ainv = A^-1 per cell (FP64 Gauss-Jordan with partial pivoting, stored FP32); flag[cell] = 1 (never cleared here) where
+// a pivot is zero or not finite or the inverse overflows FP32
+hipError_t launch_vanka_invert(int n_cells, int nd, const double *A, float *Ainv, int32_t *flag, hipStream_t s);
+// ev [n_cells][nd] = Ainv_c r[cell_dofs[c]]; then x[dof] += omega / (cells holding dof) * its slots' sum in cell order
+hipError_t launch_vanka_apply(int n_cells, int nd, const float *Ainv, const int32_t *cell_dofs, const double *r, double *ev,
+                              hipStream_t s);
+hipError_t launch_vanka_update(double *x, const double *ev, const int64_t *voff, const int64_t *vslot, int64_t nv,
+                               const int64_t *poff, const int64_t *pslot, int64_t np, int dim, double omega, hipStream_t s);
+
 }  // namespace gls

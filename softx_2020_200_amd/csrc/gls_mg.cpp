@@ -251,6 +251,10 @@ int mg_prepare(gls_ctx *c) {
     // third step: factored with the first pressure DoF pinned
     GLS_TRY(mg.coarse.factor(c->stream, (int64_t)g->dim * g->n_vnodes, banded, t0));
   }
+  // the cell-Vanka levels' patch inverses at this state (where the ILU smoothers refactor): a singular patch is
+  // reported here and leaves the hierarchy dirty
+  for (auto *g : mg.lev)
+    if (g->vanka.smooth) GLS_TRY(ensure_vanka(g));
   mg.dirty = false;
   return GLS_OK;
 }
@@ -469,6 +473,9 @@ int mg_presmooth(gls_ctx *g, hipStream_t s, int pre, double om, double *zs, cons
     GLS_TRY(ensure_ilu(g));
     GLS_TRY(apply_ilu(g, b, x));  // first sweep from x = 0: x = M^-1 b
     for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(g, x, b, y, om, zs));
+  } else if (pre > 0 && g->vanka.smooth) {
+    GLS_TRY(vanka_sweep(g, x, b, y, om, true));  // first sweep from x = 0: the residual is b
+    for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(g, x, b, y, om));
   } else if (pre > 0) {
     if (!x0_ready) HIP_TRY(gls::mg_jacobi_update(x, b, nullptr, g->diag.p, om, n, 1, s));  // first sweep from x = 0
     for (int it = 1; it < pre; ++it) GLS_TRY(smoother_sweep(g, x, b, y, om));
@@ -494,7 +501,7 @@ bool mg_first_producer_ok(gls_ctx *c, int l) {
   gls_ctx *g = mg.lev[(size_t)l];
   if (l == L - 1 && (mg.replica || mg.coarse.ok)) return false;
   const int pre = l == L - 1 ? mg.csweeps : mg.lpre[(size_t)l];
-  if (pre < 1 || g->dist.on || g->stream != c->stream) return false;
+  if (pre < 1 || g->dist.on || g->stream != c->stream || g->vanka.smooth) return false;
   if (l == L - 1 && l > 0 && pre > 1 && coarse_graph_eligible(c, g, mgbuf(c, l, MB_B), mgbuf(c, l, MB_X))) return false;
   if (pre == 1 && l < L - 1 && first_sweep_fusable(g)) return false;
   return !(mg.ilu_smooth && g->ilu.on && !g->ilu.probe_only);
@@ -713,8 +720,8 @@ static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
   mg.pre = p->pre_smooth > 0 ? p->pre_smooth : (p->pre_smooth < 0 ? 0 : 2);
   mg.post = p->post_smooth >= 0 ? p->post_smooth : 2;
   mg.csweeps = p->coarse_sweeps > 0 ? p->coarse_sweeps : 30;
-  mg.omega = p->omega > 0 ? p->omega : 0.6;
-  mg.comega = p->coarse_omega > 0 ? p->coarse_omega : mg.omega;
+  mg.omega = p->omega > 0 ? p->omega : (p->smoother == 3 ? 0.8 : 0.6);  // cell-Vanka: the best V(1,1) damping
+  mg.comega = p->coarse_omega > 0 ? p->coarse_omega : (p->smoother == 3 ? 0.6 : mg.omega);  // coarsest: Jacobi sweeps
   mg.lpre.assign((size_t)p->n_levels, mg.pre);
   mg.lpost.assign((size_t)p->n_levels, mg.post);
   if (p->level_sweeps)
@@ -732,8 +739,9 @@ static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
     for (auto *g : mg.lev) g->smooth_oseen = os && g->smooth_f32;
   }
   mg.ilu_smooth = p->smoother == 1 || p->smoother == 2;
-  if (p->smoother < 0 || p->smoother > 2 || (mg.ilu_smooth && !mg.csr))
-    return set_err(GLS_EINVAL, "mg: smoother 0 (Jacobi), 1 (ILU) or 2 (ILU below the finest level; gls_mg_attach_transfers hierarchies)");
+  if (p->smoother < 0 || p->smoother > 3 || ((mg.ilu_smooth || p->smoother == 3) && !mg.csr))
+    return set_err(GLS_EINVAL, "mg: smoother 0 (Jacobi), 1 (ILU), 2 (ILU below the finest level) or 3 (cell-Vanka); 1 - 3 on "
+                               "gls_mg_attach_transfers hierarchies");
   for (int l = 0; l < p->n_levels; ++l)
     for (int b = 0; b < MB_N; ++b) {
       mg.bufs.emplace_back(new DevBuf<double>());
@@ -750,6 +758,12 @@ static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
       GLS_TRY(gls_ilu_set_options(g, GLS_ILU_ORDER_MULTICOLOR, 0));
       GLS_TRY(gls_ilu_attach(g, 0, 1e-12, 1.0));
       mg.ilu_levels.push_back(g);  // detached again by gls_mg_detach
+    }
+  if (p->smoother == 3)  // additive cell-Vanka on every level above the coarsest: the maps now, the inverses per state
+    for (int l = 0; l + 1 < p->n_levels; ++l) {
+      gls_ctx *g = mg.lev[(size_t)l];
+      GLS_TRY(vanka_attach(g));
+      g->vanka.smooth = true;
     }
   // direct coarsest solve: single GPU, coarsest level up to kDirectMax DoFs (FP64 LU up to kDirectSmall, FP32 above)
   {
@@ -774,6 +788,9 @@ static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
 int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
   GLS_TRY(check_ctx(c));
   if (!p || p->n_levels < 2 || !p->levels || p->levels[0] != c) return set_err(GLS_EINVAL, "mg: levels[0] must be ctx");
+  if (p->smoother == 3)
+    return set_err(GLS_EINVAL, "mg: the cell-Vanka smoother (3) needs a gls_mg_attach_transfers hierarchy of per-cell "
+                               "contexts, not the nested brick (pencil) levels");
   if (c->dim != 3 || c->k > 2 || c->k != c->kp) return set_err(GLS_EINVAL, "mg: 3D Q1-Q1 / Q2-Q2 only");
   if (c->hang.on) return set_err(GLS_EINVAL, "mg: not with hanging-node constraints");
   if (c->map_degree > 0) return set_err(GLS_EINVAL, "mg: nested hyper_cube levels only (not mapped cells)");
@@ -872,6 +889,24 @@ int gls_mg_attach_transfers(gls_ctx *c, const gls_mg_params *p, const int64_t *c
   GLS_TRY(check_ctx(c));
   if (!p || p->n_levels < 2 || !p->levels || p->levels[0] != c) return set_err(GLS_EINVAL, "mg: levels[0] must be ctx");
   if (!p_off || !p_col || !p_w || !inject) return set_err(GLS_EINVAL, "mg: transfer arrays missing");
+  if (p->smoother == 3) {  // refused before anything is detached: the context keeps what it had
+    for (int l = 0; l + 1 < p->n_levels; ++l) {
+      if (!p->levels[l]) return set_err(GLS_EINVAL, "mg level %d: null", l);
+      if (const char *why = vanka_refusal(p->levels[l])) return set_err(GLS_EINVAL, "mg level %d: %s", l, why);
+    }
+    // the maps too (they refuse a cell that holds a node twice); a refusal drops the maps built here
+    std::vector<gls_ctx *> built;
+    for (int l = 0; l + 1 < p->n_levels; ++l) {
+      gls_ctx *g = p->levels[l];
+      if (g->vanka.on) continue;
+      const int rc = vanka_attach(g);
+      if (rc < 0) {
+        for (auto *b : built) b->vanka = gls_ctx::Vanka();
+        return rc;
+      }
+      built.push_back(g);
+    }
+  }
 
   GLS_TRY(gls_mg_detach(c));  // a previous attach's levels / smoother ILUs
   auto &mg = c->mg;
@@ -976,6 +1011,7 @@ int gls_mg_attach_replica(gls_ctx *c, const gls_mg_params *p, gls_ctx *replica, 
   GLS_TRY(check_ctx(c));
   if (!p || !replica || replica == c || replica->dist.on || !p_off || !p_col || !p_w || !inject)
     return set_err(GLS_EINVAL, "mg replica attach: arguments");
+  if (p->smoother == 3) return set_err(GLS_EINVAL, "mg replica attach: the cell-Vanka smoother (3) runs on one rank only");
   if (!c->dist.on) return set_err(GLS_EINVAL, "mg replica attach: the fine context is not distributed");
   if (replica->dim != c->dim || replica->k != c->k || replica->kp != c->kp)
     return set_err(GLS_EINVAL, "mg replica attach: replica order / dimension differs");
@@ -1077,6 +1113,11 @@ int gls_mg_detach(gls_ctx *c) {
   // the ILU(0) smoothers the attach put on the levels (level 0 is this context) go with the multigrid, so
   // the preconditioner falls back to Jacobi (gls_native.h) and not to a leftover smoother ILU
   for (auto *g : c->mg.ilu_levels) GLS_TRY(gls_ilu_detach(g));
+  for (auto *g : c->mg.lev)  // and the cell-Vanka maps, matrices and inverses of the levels it smoothed
+    if (g->vanka.smooth) {
+      HIP_TRY(hipStreamSynchronize(g->stream));
+      g->vanka = gls_ctx::Vanka();
+    }
   c->mg = gls_ctx::MG();  // (CoarseSolve's assignment ends a coarse factorization in flight first)
   return GLS_OK;
 }

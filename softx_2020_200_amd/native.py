@@ -53,6 +53,8 @@ EXPORTS = [
     "gls_flow_diagnostics", "gls_time_control_create", "gls_time_control_destroy", "gls_time_control_integrate",
     "gls_time_control_set_cfl", "gls_time_control_get", "gls_time_control_is_output_iteration",
     "gls_output_plan_create", "gls_output_plan_destroy", "gls_output_fields", "gls_vtu_write_device",
+    "gls_vanka_sizes", "gls_vanka_element_matrices", "gls_vanka_patch_inverses", "gls_vanka_sweep", "gls_vanka_detach",
+    "gls_vanka_maps",
 ]
 
 
@@ -202,6 +204,13 @@ def load():
     L.gls_mg_attach_replica.argtypes = [vp, C.POINTER(MGParams), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.gls_mg_transfer.argtypes = [vp, C.c_int, C.c_int, vp, vp]
+    L.gls_vanka_sizes.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.gls_vanka_element_matrices.argtypes = [vp, vp]
+    L.gls_vanka_patch_inverses.argtypes = [vp, vp, vp]
+    L.gls_vanka_sweep.argtypes = [vp, vp, vp, C.c_double]
+    L.gls_vanka_detach.argtypes = [vp]
+    L.gls_vanka_maps.argtypes = [C.c_int] * 3 + [i64] * 3 + [C.POINTER(C.c_int32)] * 4 + [C.POINTER(i64), C.POINTER(C.c_int32), i64,
+                                 C.POINTER(i64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i64, C.POINTER(i64), C.POINTER(i64)]
     L.gls_mg_residual_restrict.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
     L.gls_mg_prolong_smooth.argtypes = [vp, C.c_int, vp, vp, vp, C.c_double, C.POINTER(C.c_int)]
     P64 = C.POINTER(i64)
@@ -889,7 +898,8 @@ class GLSContext:
                                    mixed_precision=0):
         """The V-cycle on a general hierarchy (gls_mg_attach_transfers): levels [self] + coarse_levels
         (hanging lines set on each), transfers[l] = (off, col, w, inject) from level l+1 to level l
-        (octree_mg_transfer). Smoothing: damped Jacobi, or smoother="ilu" (ILU(0) per level); mixed_precision=1:
+        (octree_mg_transfer). Smoothing: damped Jacobi, smoother="ilu" (ILU(0) per level) or smoother="vanka" (the
+        additive cell-Vanka smoother, gls_mg_params.smoother = 3; omega=0.0 takes its default 0.8); mixed_precision=1:
         the levels' forest bricks apply the pencil J.v in FP32 (the other cells stay FP64)."""
         levels = [self] + list(coarse_levels)
         if len(transfers) != len(levels) - 1:
@@ -911,7 +921,8 @@ class GLSContext:
         ws = (PD * len(keep))(*[k[2].ctypes.data_as(PD) for k in keep])
         injs = (P64 * len(keep))(*[k[3].ctypes.data_as(P64) for k in keep])
         p = MGParams(len(levels), C.cast(arr, C.POINTER(C.c_void_p)), pre_smooth, post_smooth, coarse_sweeps, omega,
-                     coarse_omega, coarse_direct, int(mixed_precision), ls, {"jacobi": 0, "ilu": 1, "ilu-coarse": 2}[smoother])
+                     coarse_omega, coarse_direct, int(mixed_precision), ls,
+                     {"jacobi": 0, "ilu": 1, "ilu-coarse": 2, "vanka": 3}[smoother])
         check(self.L.gls_mg_attach_transfers(self.h, C.byref(p), offs, cols, ws, injs), "gls_mg_attach_transfers")
         self._mg_levels = levels
 
@@ -926,7 +937,7 @@ class GLSContext:
                 np.ascontiguousarray(p_w, np.float64), np.ascontiguousarray(inject_local, np.int64))
         arr = (C.c_void_p * 1)(self.h)
         p = MGParams(1, C.cast(arr, C.POINTER(C.c_void_p)), pre_smooth, post_smooth, 0, omega, 0.0, int(coarse_direct), 0,
-                     None, {"jacobi": 0, "ilu": 1}[smoother], 0)
+                     None, {"jacobi": 0, "ilu": 1, "vanka": 3}[smoother], 0)
         check(self.L.gls_mg_attach_replica(self.h, C.byref(p), replica.h, keep[0].ctypes.data_as(C.POINTER(C.c_int64)),
                                            keep[1].ctypes.data_as(C.POINTER(C.c_int32)),
                                            keep[2].ctypes.data_as(C.POINTER(C.c_double)),
@@ -941,6 +952,38 @@ class GLSContext:
         check(self.L.gls_mg_set_coarse_replica(self.h, replica.h, len(m), m.ctypes.data_as(C.POINTER(C.c_int64))),
               "gls_mg_set_coarse_replica")
         self._coarse_replica = replica
+
+    def vanka_sizes(self):
+        """(DoFs per cell, padded row length in floats of the FP32 patch inverses) (gls_vanka_sizes)."""
+        nd, ld = C.c_int(0), C.c_int(0)
+        check(self.L.gls_vanka_sizes(self.h, C.byref(nd), C.byref(ld)), "gls_vanka_sizes")
+        return nd.value, ld.value
+
+    def vanka_element_matrices(self):
+        """The cells' local Jacobians [n_cells, nd, nd] at the current state (gls_vanka_element_matrices)."""
+        import torch
+        nd, _ = self.vanka_sizes()
+        K = torch.empty((self.n_cells, nd, nd), dtype=torch.float64, device="cuda")
+        check(self.L.gls_vanka_element_matrices(self.h, _ptr(K)), "gls_vanka_element_matrices")
+        return K
+
+    def vanka_patch_inverses(self):
+        """(A [n_cells, nd, nd] FP64, Ainv [n_cells, nd, row floats] FP32): the assembled Jacobian on each cell's DoFs
+        and its inverse, rebuilt when the Jacobian's state changed (gls_vanka_patch_inverses)."""
+        import torch
+        nd, ld = self.vanka_sizes()
+        A = torch.empty((self.n_cells, nd, nd), dtype=torch.float64, device="cuda")
+        Ai = torch.empty((self.n_cells, nd, ld), dtype=torch.float32, device="cuda")
+        check(self.L.gls_vanka_patch_inverses(self.h, _ptr(A), C.c_void_p(Ai.data_ptr())), "gls_vanka_patch_inverses")
+        return A, Ai
+
+    def vanka_sweep(self, x, b, omega=0.8):
+        """One additive cell-Vanka sweep on x in place for the right-hand side b (gls_vanka_sweep)."""
+        check(self.L.gls_vanka_sweep(self.h, _ptr(x), _ptr(b), float(omega)), "gls_vanka_sweep")
+        return x
+
+    def vanka_detach(self):
+        check(self.L.gls_vanka_detach(self.h), "gls_vanka_detach")
 
     def mg_smoother_apply(self, v, out=None):
         """y = A_s v with the operator the attached V-cycle smooths this level with (gls_mg_smoother_apply)."""
@@ -1536,3 +1579,29 @@ def cuthill_mckee(adj_off, adj, dof_off, dofs):
     L.gls_cuthill_mckee.argtypes = [C.c_int64] + [C.c_void_p] * 5
     check(L.gls_cuthill_mckee(len(a[0]) - 1, *(x.ctypes.data for x in a), order.ctypes.data), "gls_cuthill_mckee")
     return order
+
+
+def vanka_maps(dim, k, kp, cell_vnodes, cell_pnodes, n_vnodes, n_pnodes):
+    """Host only: the cell-Vanka patch maps of a mesh (gls_vanka_maps) as a dict: cell_dofs [n_cells, nd], mult
+    [n_dofs], nb_off, nb_cell, ov_off, ov_i, ov_j."""
+    L = load()
+    cv = np.ascontiguousarray(cell_vnodes, dtype=np.int32)
+    cp = None if cell_pnodes is None else np.ascontiguousarray(cell_pnodes, dtype=np.int32)
+    nc = cv.shape[0]
+    nd = dim * (k + 1) ** dim + (kp + 1) ** dim
+    pi32, pi64, pu8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    cvp = cv.ctypes.data_as(pi32)
+    cpp = cp.ctypes.data_as(pi32) if cp is not None else pi32()
+    npair, nov = C.c_int64(0), C.c_int64(0)
+    check(L.gls_vanka_maps(dim, k, kp, nc, n_vnodes, n_pnodes, cvp, cpp, pi32(), pi32(), pi64(), pi32(), 0, pi64(), pu8(), pu8(),
+                           0, C.byref(npair), C.byref(nov)), "gls_vanka_maps")
+    n_dofs = dim * n_vnodes + (n_pnodes if cp is not None else n_vnodes)
+    out = {"cell_dofs": np.zeros((nc, nd), np.int32), "mult": np.zeros(n_dofs, np.int32), "nb_off": np.zeros(nc + 1, np.int64),
+           "nb_cell": np.zeros(npair.value, np.int32), "ov_off": np.zeros(npair.value + 1, np.int64),
+           "ov_i": np.zeros(nov.value, np.uint8), "ov_j": np.zeros(nov.value, np.uint8)}
+    check(L.gls_vanka_maps(dim, k, kp, nc, n_vnodes, n_pnodes, cvp, cpp, out["cell_dofs"].ctypes.data_as(pi32),
+                           out["mult"].ctypes.data_as(pi32), out["nb_off"].ctypes.data_as(pi64),
+                           out["nb_cell"].ctypes.data_as(pi32), npair.value, out["ov_off"].ctypes.data_as(pi64),
+                           out["ov_i"].ctypes.data_as(pu8), out["ov_j"].ctypes.data_as(pu8), nov.value, C.byref(npair),
+                           C.byref(nov)), "gls_vanka_maps")
+    return out
