@@ -12,7 +12,7 @@
 // Results are printed as `key = value` lines and a final error table (own format); the numbers
 // are what the parity tests compare with the reference's outputs.
 //
-// Usage: gls_navier_stokes [--dim 2|3] [--precond mg|jacobi] file.prm
+// Usage: gls_navier_stokes [--dim 2|3] [--precond mg|jacobi] [--coarse-storage auto|dense|band] file.prm (all options: main)
 // Scope: mesh type dealii / grid type hyper_cube (+ initial refinement; steady "number mesh adapt"
 // with mesh adaptation type uniform, or kelly = Kelly-driven refinement and coarsening on a forest
 // with hanging nodes, any number of levels); bc types noslip, function, periodic, slip.
@@ -1169,6 +1169,8 @@ struct Solver {
     release_boundary_plan();  // the plan belongs to the context destroyed below
     release_output_plan();
     release_error_plan();
+    // the hierarchy goes before its levels: a coarse factorization in flight reads the coarsest level's probed CSR
+    if (ctx && !mg_levels.empty()) (void)gls_mg_detach(ctx);
     for (gls_ctx *g : mg_levels) gls_destroy(g);
     mg_levels.clear();
     for (gls_refined_mesh *R : mg_meshes) gls_octree_mesh_destroy(R);
@@ -1717,8 +1719,9 @@ struct Solver {
   }
   // gls_mg_attach_transfers with the requested smoother; where the library refuses it (GLS_EINVAL: a level with
   // hanging or slip lines under the cell-Vanka smoother, ...) the present choice, said on stderr
-  void attach_transfers_with_smoother(gls_ctx *c, gls_mg_params mp, const int64_t *const *po, const int32_t *const *pc,
-                                      const double *const *pw, const int64_t *const *pi, const char *what) {
+  // (fatal = false: a remaining GLS_EINVAL is returned, for the banded coarse LU's fallback)
+  int attach_transfers_with_smoother(gls_ctx *c, gls_mg_params mp, const int64_t *const *po, const int32_t *const *pc,
+                                     const double *const *pw, const int64_t *const *pi, const char *what, bool fatal = true) {
     mg_smoother_params(mp, false);
     int rc = gls_mg_attach_transfers(c, &mp, po, pc, pw, pi);
     if (rc == GLS_EINVAL && mg_smoother >= 0) {
@@ -1728,7 +1731,8 @@ struct Solver {
       mg_smoother_params(mp, true);
       rc = gls_mg_attach_transfers(c, &mp, po, pc, pw, pi);
     }
-    ck(rc, what);
+    if (fatal || rc != GLS_EINVAL) ck(rc, what);
+    return rc;
   }
 
   // Geometric multigrid on the triangulation's refinement hierarchy (gls_mg_attach_transfers): levels =
@@ -1740,8 +1744,16 @@ struct Solver {
   // the dense LU (<= kPLevelDirectMax DoFs) -- whenever the base level is too large for the LU itself; this is also
   // the whole hierarchy of an unrefined mesh (the reference's setup_AMG, gls_navier_stokes.cc:1180-1240: an
   // algebraic multilevel preconditioner there, a geometric / polynomial one here, announced on stderr).
+  // --coarse-storage auto | dense | band: above kPLevelDirectMax the coarsest level's LU takes band storage
+  // (gls_mg_params.coarse_direct: block-tridiagonal FP32 panels from the probed CSR, no n x n array) when the library
+  // finds room for it -- auto; where it does not, what dense does, with the reason on stderr. dense: the caps above
+  // (no p-level beyond 40000 DoFs; a larger coarsest level takes 30 Jacobi sweeps). band: band storage at any size.
+  // With --np, auto is dense and band is refused (the replicated levels keep their dense caps).
   static constexpr int64_t kPLevelDirectMax = 40000;
   bool plevel_used = false;
+  int coarse_storage = 0;       // --coarse-storage: 0 auto, 1 dense, 2 band
+  int coarse_mode() const { return world == 1 ? coarse_storage : 1; }
+  std::string coarse_band_note;  // the announcement's words for a banded coarse LU ("" otherwise)
   void attach_umesh_mg() {
     int L = 0;
     for (int64_t c = 0; c < space->n_cells; ++c) L = std::max(L, (int)space->cell_level[c]);
@@ -1779,7 +1791,7 @@ struct Solver {
       gls_umesh_destroy(uc);
       ck(rc, "gls_umesh_fe_space (p-level)");
       const Mesh r = mesh_of_space(*s_, 1, 1);
-      if (r.n_dofs() <= kPLevelDirectMax) {
+      if (r.n_dofs() <= kPLevelDirectMax || coarse_mode() != 1) {
         spaces.push_back(s_);
         sp.push_back(s_);
         const Constraints cc = make_constraints(P, r, time);
@@ -1828,9 +1840,44 @@ struct Solver {
     std::memset(&mp, 0, sizeof(mp));
     mp.n_levels = (int)lv.size();
     mp.levels = lv.data();
-    mp.coarse_direct = n_coarse <= (plevel_used ? kPLevelDirectMax : 8192) ? 1 : -1;
+    // 1 above kPLevelDirectMax: the library's band route (auto only; it refuses when the panels do not fit)
+    auto direct_for = [&](int64_t n, bool plevel) {
+      if (coarse_mode() == 2) return 2;
+      if (n <= (plevel ? kPLevelDirectMax : 8192)) return 1;
+      return coarse_mode() == 0 && n > kPLevelDirectMax ? 1 : -1;
+    };
+    mp.coarse_direct = direct_for(n_coarse, plevel_used);
+    coarse_band_note.clear();
     if (world == 1) {
-      attach_transfers_with_smoother(ctx, mp, po.data(), pc.data(), pw.data(), pi.data(), "gls_mg_attach_transfers");
+      const bool band_try = coarse_mode() == 0 && n_coarse > kPLevelDirectMax;
+      const int rc = attach_transfers_with_smoother(ctx, mp, po.data(), pc.data(), pw.data(), pi.data(),
+                                                    "gls_mg_attach_transfers", !band_try);
+      if (rc == GLS_EINVAL) {  // auto: no room for the panels -- what --coarse-storage dense does
+        std::fprintf(stderr, "banded coarse LU not used (%s): %s\n", gls_last_error(),
+                     plevel_used ? "no p-level, the base level is the coarsest" : "Jacobi sweeps on the coarsest level");
+        ck(gls_mg_detach(ctx), "gls_mg_detach");  // (a refusal before the library's own detach keeps what was attached)
+        if (plevel_used) {
+          gls_destroy(mg_levels.back());
+          mg_levels.pop_back();
+          lv.pop_back();
+          plevel_used = false;
+        }
+        if (lv.size() < 2) return;
+        ck(gls_n_dofs(lv.back(), &n_coarse), "gls_n_dofs");
+        mp.n_levels = (int)lv.size();
+        mp.coarse_direct = n_coarse <= 8192 ? 1 : -1;
+        attach_transfers_with_smoother(ctx, mp, po.data(), pc.data(), pw.data(), pi.data(), "gls_mg_attach_transfers");
+        return;
+      }
+      int64_t cn = 0, bl = 0, bu = 0, bytes = 0;
+      int band = 0;
+      ck(gls_mg_coarse_info(ctx, &cn, &band, &bl, &bu, nullptr, &bytes), "gls_mg_coarse_info");
+      if (band) {
+        char note[160];
+        std::snprintf(note, sizeof note, "banded LU (n %lld, bandwidths %lld/%lld, %.2f GB)", (long long)cn, (long long)bl,
+                      (long long)bu, (double)bytes * 1e-9);
+        coarse_band_note = note;
+      }
       return;
     }
     if (mg_smoother == 3 && rank == 0)
@@ -2193,13 +2240,17 @@ struct Solver {
     if (rank != 0) return;
     const char *meth[3] = {"gmres", "bicgstab", "amg"};
     const char *krylov = P.lin_method == 1 ? "BiCGStab" : "GMRES";
-    char prec[256];
+    char prec[384];
+    const std::string coarse_words = plevel_used ? ", the last a Q1-Q1 p-level on the base mesh, " +
+                                                       (coarse_band_note.empty() ? std::string("dense LU") : coarse_band_note)
+                                     : coarse_band_note.empty() ? std::string()
+                                                                : ", the coarsest by a " + coarse_band_note;
     if (!mg_levels.empty() && (rmesh || space))
       std::snprintf(prec, sizeof prec, "geometric multigrid V(%d,%d)-cycle with %s smoothing on the %s refinement hierarchy (%zu levels%s)",
                     mg_sweeps_used, mg_sweeps_used,
                     mg_smoother_used == 3 ? "additive cell-Vanka" : mg_smoother_used ? "ILU(0)" : "damped-Jacobi",
                     rmesh ? "forest's" : "triangulation's", mg_levels.size() + 1,
-                    plevel_used ? ", the last a Q1-Q1 p-level on the base mesh, dense LU" : "");
+                    coarse_words.c_str());
     else if (!mg_levels.empty())
       std::snprintf(prec, sizeof prec, "geometric multigrid V(1,1)-cycle on the nested hyper_cubes");
     else if (use_ilu && P.lin_method == 2)
@@ -3254,6 +3305,8 @@ int main(int argc, char **argv) {
   // multigrid on adapted meshes; hmg: that multigrid for every method and order), --mg-smoother ilu|jacobi|vanka and
   // --mg-sweeps N (the hierarchy multigrid's smoother and its pre / post sweeps; default: ILU(0) V(1,1) on Q2-Q1, damped
   // Jacobi V(2,2) on equal order), --precision N (error table digits),
+  // --coarse-storage auto|dense|band (the hierarchy multigrid's coarsest-level LU: band storage above 40000 DoFs when it
+  // fits, today's dense caps, or band storage at any size),
   // --stats (solver iteration totals), --ilu-block-dofs N (block-Jacobi ILU subdomains of N DoFs,
   // 0 = one block), --ilu-order cm|multicolor (gls_ilu_set_options), --dump DIR (every iteration's
   // final state for the pipeline tests), --output-eval host|device (the VTU point data from the host vector or,
@@ -3269,6 +3322,7 @@ int main(int argc, char **argv) {
   int np_ranks = 1;
   int forest_mode = 0;
   int mg_smoother = -1, mg_sweeps = 0;
+  int coarse_storage = 0;
   int precision = 4;
   const char *file = nullptr;
   const std::string prog = argv[0];
@@ -3296,6 +3350,13 @@ int main(int argc, char **argv) {
     }
     else if (!std::strcmp(argv[i], "--precision") && i + 1 < argc) precision = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--stats")) stats = true;
+    else if (!std::strcmp(argv[i], "--coarse-storage") && i + 1 < argc) {
+      const char *v = argv[++i];
+      if (!std::strcmp(v, "auto")) coarse_storage = 0;
+      else if (!std::strcmp(v, "dense")) coarse_storage = 1;
+      else if (!std::strcmp(v, "band")) coarse_storage = 2;
+      else die("--coarse-storage %s: auto, dense or band", v);
+    }
     else if (!std::strcmp(argv[i], "--ilu-block-dofs") && i + 1 < argc) ilu_block = std::atoll(argv[++i]);
     else if (!std::strcmp(argv[i], "--dump") && i + 1 < argc) dump = argv[++i];
     else if (!std::strcmp(argv[i], "--np") && i + 1 < argc) np_ranks = std::atoi(argv[++i]);
@@ -3335,6 +3396,7 @@ int main(int argc, char **argv) {
   // --np N: N ranks forked here, before any GPU call (the children's stdout is discarded: rank 0
   // prints, as the reference's pcout does)
   if (np_ranks < 1 || np_ranks > kMaxRanks) die("--np must be in 1..%d", kMaxRanks);
+  if (coarse_storage == 2 && np_ranks > 1) die("--coarse-storage band runs on one rank (--np 1)");
   int rank = 0;
   std::vector<pid_t> kids;
   if (np_ranks > 1) {
@@ -3358,6 +3420,7 @@ int main(int argc, char **argv) {
   s.forest_mode = forest_mode;
   s.mg_smoother = mg_smoother;
   s.mg_sweeps = mg_sweeps;
+  s.coarse_storage = coarse_storage;
   s.rank = rank;
   s.world = np_ranks;
   if (np_ranks > 1) {

@@ -219,7 +219,21 @@ typedef struct {
                                                  setup), applied by blocked triangular solves; checked
                                                  by |A x - 1| / |1|: < 1e-2 as it is, < 0.5 with one
                                                  refinement step against the FP64 matrix, else pivoted
-                                                 FP32 LU + explicit inverse */
+                                                 FP32 LU + explicit inverse.
+                                                 1 above 40000 DoFs, or 2 at any size: the band route
+                                                 (gls_band_lu_* below) -- the FP32 matrix in block-
+                                                 tridiagonal storage filled from the probing ILU's CSR,
+                                                 no n x n array; same check and refinement against the
+                                                 FP64 CSR, no pivoted fallback (a failed check is
+                                                 GLS_EINVAL at the first coarse solve and the hierarchy
+                                                 prepares again). It needs a coarsest level probed
+                                                 through its ILU CSR (a per-cell context without an ILU
+                                                 or hierarchy of its own, gls_mg_attach_transfers;
+                                                 not a gls_mg_attach_replica level) whose panels plus CSR take at most half of
+                                                 the free device memory at attach (or
+                                                 GLS_MG_BAND_MAX_BYTES, if less); else GLS_EINVAL
+                                                 (a brick or column-probed level: before anything is
+                                                 detached). GLS_MG_VERBOSE prints a `band storage` line */
   int mixed_precision;                        /* 1: the V-cycle's smoothing / residual J.v run in FP32
                                                  arithmetic from an FP32 copy of the linearization
                                                  (brick path; vectors, transfers and the outer GMRES
@@ -279,6 +293,11 @@ int gls_mg_attach_transfers(gls_ctx *ctx, const gls_mg_params *prm, const int64_
  * every rank; levels / other coarse entries are not used. Host arrays. */
 int gls_mg_attach_replica(gls_ctx *ctx, const gls_mg_params *prm, gls_ctx *replica, const int64_t *p_off,
                           const int32_t *p_col, const double *p_w, const int64_t *inject);
+/* The attached hierarchy's direct coarse solve: *n its unknowns (0: none, the coarsest level is smoothed), *storage 0
+ * dense arrays, 1 band storage; bl / bu / nb the band route's bandwidths and block width (-1 otherwise), *bytes the
+ * matrix storage held (dense: the FP64 array plus the FP32 one above 8192 DoFs; band: the panels). Any output may be
+ * NULL. */
+int gls_mg_coarse_info(gls_ctx *ctx, int64_t *n, int *storage, int64_t *bl, int64_t *bu, int64_t *nb, int64_t *bytes);
 /* z = M^-1 v with the preconditioner gls_solve_linear uses at the current state (the V-cycle when
  * attached, else Jacobi): the reference's preconditioner vmult (DEVICE pointers, no aliasing). */
 int gls_apply_preconditioner(gls_ctx *ctx, const double *v, double *z);
@@ -356,6 +375,32 @@ int gls_vanka_element_matrices(gls_ctx *ctx, double *K);
 int gls_vanka_patch_inverses(gls_ctx *ctx, double *A, float *Ainv);
 int gls_vanka_sweep(gls_ctx *ctx, double *x, const double *b, double omega);
 int gls_vanka_detach(gls_ctx *ctx);
+
+/* Band-storage FP32 LU: the coarsest multigrid level's exact solve above 40000 DoFs (coarse_direct in gls_mg_params)
+ * on its own, for tests and tools. An n x n matrix with lower / upper bandwidths bl / bu is kept as block columns
+ * nb >= max(bl, bu, 1) wide, each one contiguous 3 nb x nb column-major panel [U_{k-1}; D_k; L_k] (3 n nb floats; no
+ * n x n array in any precision), factored without pivoting by rocSOLVER / rocBLAS block calls and applied by a
+ * forward / backward substitution on the panels (2 ceil(n / 128) launches, sums in a fixed order: two solves of the
+ * same input are bitwise equal). There is no pivoted fallback: the factor is checked by |A x - 1| / |1| against the
+ * FP64 CSR and refused (GLS_EINVAL naming the value) from 0.5 up or when not finite.
+ *   gls_band_lu_layout : HOST only, no GPU. block = 0: nb = max(bl, bu) rounded up to a multiple of 256, at least
+ *                        512; block > 0: nb = block, a multiple of 128 not narrower than the band. n_blocks =
+ *                        ceil(n / nb), n_floats = 3 n nb (exact in 64 bits). n <= 0, a bandwidth outside 0 .. n - 1 or
+ *                        a bad block: GLS_EINVAL.
+ *   gls_band_lu_create : HOST CSR in FP64 (rowp of n + 1, col, val; no duplicate entries), rounded to FP32 into the
+ *                        panels with row and column pin replaced by identity (pin < 0: none), factored and checked;
+ *                        synchronous, on the default stream.
+ *   gls_band_lu_solve  : x = A^-1 b on DEVICE vectors of n doubles (b == x allowed), x[pin] = 0; refine != 0: one
+ *                        step of iterative refinement x += LU^-1 (b - A x) against the FP64 CSR. Queued on the
+ *                        default stream.
+ *   gls_band_lu_info   : the CSR's bandwidths, nb, the panels' bytes and the check's value; any output may be NULL. */
+typedef struct gls_band_lu gls_band_lu;
+int gls_band_lu_layout(int64_t n, int64_t bl, int64_t bu, int64_t block, int64_t *nb, int64_t *n_blocks, int64_t *n_floats);
+int gls_band_lu_create(int64_t n, const int64_t *rowp, const int32_t *col, const double *val, int64_t pin, int64_t block,
+                       gls_band_lu **handle);
+int gls_band_lu_solve(gls_band_lu *handle, const double *b, double *x, int refine);
+int gls_band_lu_info(const gls_band_lu *handle, int64_t *bl, int64_t *bu, int64_t *nb, int64_t *bytes, double *check);
+int gls_band_lu_destroy(gls_band_lu *handle);
 int gls_vanka_maps(int dim, int k, int kp, int64_t n_cells, int64_t n_vnodes, int64_t n_pnodes, const int32_t *cell_vnodes,
                    const int32_t *cell_pnodes, int32_t *cell_dofs, int32_t *mult, int64_t *nb_off, int32_t *nb_cell,
                    int64_t nb_capacity, int64_t *ov_off, uint8_t *ov_i, uint8_t *ov_j, int64_t ov_capacity,

@@ -106,6 +106,60 @@ int mg_probe_setup(gls_ctx *c, gls_ctx *g) {
   mg.probe_ilu = g;
   return GLS_OK;
 }
+// ---- the band route of the direct coarse solve (coarse_direct 2, or 1 above kDirectMax): the FP32 matrix in
+// block-tridiagonal storage, filled from the probing ILU's CSR (gls_band_lu.hpp)
+bool band_route_wanted(const gls_mg_params *p, const gls_ctx *g) {
+  return p->coarse_direct == 2 || (p->coarse_direct == 1 && g->n_dofs > kDirectMax);
+}
+// the panels plus the CSR may take this fraction of the free device memory at attach
+constexpr double kBandMemFraction = 0.5;
+int band_fits(const char *who, int64_t n, size_t panel_bytes, size_t csr_bytes, const char *bound) {
+  size_t fr = 0, tot = 0;
+  HIP_TRY(hipMemGetInfo(&fr, &tot));
+  double limit = kBandMemFraction * (double)fr;
+  if (const char *e = std::getenv("GLS_MG_BAND_MAX_BYTES")) limit = std::min(limit, std::atof(e));  // a caller's lower cap
+  if ((double)panel_bytes + (double)csr_bytes <= limit) return GLS_OK;
+  return set_err(GLS_EINVAL, "%s: band storage of the coarsest level (n %lld) needs %s%zu bytes of panels + %zu of CSR, "
+                             "above the limit of %.0f (half of the %zu bytes free, or GLS_MG_BAND_MAX_BYTES)", who,
+                 (long long)n, bound, panel_bytes, csr_bytes, limit, fr);
+}
+// what can be refused before anything is detached: a coarsest level g that mg_probe_setup would not probe through an
+// ILU CSR (an ILU attached by this context's own multigrid goes with the detach), and panels that cannot fit even
+// at the narrowest block (the bandwidths are known only once the probing ILU is attached: mg_coarse_setup)
+int band_precheck(const char *who, gls_ctx *c, const gls_mg_params *p, gls_ctx *g) {
+  if (!g || !band_route_wanted(p, g)) return GLS_OK;
+  const auto &own = c->mg.ilu_levels;
+  const char *why = g->use_brick && g->use_qdata ? "it runs the brick kernels and is probed by them"
+                    : g->dist.on                 ? "it is distributed"
+                    : g->mg.on                   ? "it has a hierarchy of its own"
+                    : g->ilu.on && std::find(own.begin(), own.end(), g) == own.end()
+                        ? "it has an ILU of its own and is probed column by column"
+                        : nullptr;
+  if (why)
+    return set_err(GLS_EINVAL, "%s: coarse_direct %d on %lld DoFs takes band storage, which needs a coarsest level probed "
+                               "through its ILU CSR: %s", who, p->coarse_direct, (long long)g->n_dofs, why);
+  return band_fits(who, g->n_dofs, sizeof(float) * (size_t)(3 * g->n_dofs * kBandSub), 0, "at least ");
+}
+int mg_probe_band(gls_ctx *c, gls_ctx *g);
+// the direct coarse solve's storage and probing pattern on the coarsest level g
+int mg_coarse_setup(const char *who, gls_ctx *c, gls_ctx *g, bool band) {
+  auto &mg = c->mg;
+  if (!band) {
+    GLS_TRY(mg.coarse.init(g->n_dofs));
+    return mg_probe_setup(c, g);
+  }
+  GLS_TRY(mg_probe_setup(c, g));
+  if (mg.probe_ilu != g) return set_err(GLS_EINVAL, "%s: band storage needs a coarsest level probed through its ILU CSR", who);
+  GLS_TRY(mg_probe_band(c, g));  // the bandwidths of the CSR's Cuthill-McKee order
+  const char *e = std::getenv("GLS_MG_BAND_BLOCK");  // the block width (a multiple of 128; default: by the band)
+  const int64_t block = e ? std::atoll(e) : 0;
+  BandLayout L;
+  if (const char *why = band_layout(g->n_dofs, mg.coarse.band.bl, mg.coarse.band.bu, block, &L))
+    return set_err(GLS_EINVAL, "%s: coarse band storage: %s", who, why);
+  const size_t csr = (size_t)g->ilu.nnz * (sizeof(double) + sizeof(int32_t)) + ((size_t)g->n_dofs + 1) * sizeof(int64_t);
+  GLS_TRY(band_fits(who, g->n_dofs, sizeof(float) * (size_t)L.n_floats, csr, ""));
+  return mg.coarse.init_band(g->n_dofs, block);
+}
 // first step of the preparation: the levels re-discretised at the Jacobian's state (the frozen snapshot under
 // skip_newton): injected state and history, time data, diagonal; the replicas take theirs summed over ranks
 int mg_prepare_levels(gls_ctx *c) {
@@ -235,12 +289,19 @@ namespace gls_impl {  // declared in gls_ctx.hpp
 int mg_prepare(gls_ctx *c) {
   auto &mg = c->mg;
   if (!mg.dirty) return GLS_OK;
-  GLS_TRY(mg.coarse.finish(c->stream));  // (its buffers are re-probed below)
+  // (its buffers are re-probed below; a failed check of the band route's superseded factor is not this state's error)
+  if (const int rc = mg.coarse.finish(c->stream); rc < 0 && !(mg.coarse.band_store && rc == GLS_EINVAL)) return rc;
   if (std::getenv("GLS_MG_VERBOSE")) (void)hipStreamSynchronize(c->stream);  // host wall time of the phases
   const auto t0 = CoarseSolve::Clock::now();
   GLS_TRY(mg_prepare_levels(c));
   mg.coarse.ok = false;
-  if (mg.direct) {
+  if (mg.direct && mg.coarse.band_store) {  // band storage: the probed CSR itself is the matrix, no dense array
+    gls_ctx *g = mg.rep_csr ? mg.rep2 : mg.lev.back();
+    GLS_TRY(ensure_diag(g));
+    GLS_TRY(ilu_probe(g));
+    const auto &I = g->ilu;
+    GLS_TRY(mg.coarse.factor_band(c->stream, I.rowp.p, I.col.p, I.val.p, (int64_t)g->dim * g->n_vnodes, t0));
+  } else if (mg.direct) {
     // coarsest level: the last one, or the whole-mesh replica below a distributed fine level (rep_csr)
     gls_ctx *g = mg.rep_csr ? mg.rep2 : mg.lev.back();
     double *A = mg.coarse.matrix();
@@ -765,16 +826,22 @@ static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
       GLS_TRY(vanka_attach(g));
       g->vanka.smooth = true;
     }
-  // direct coarsest solve: single GPU, coarsest level up to kDirectMax DoFs (FP64 LU up to kDirectSmall, FP32 above)
+  // direct coarsest solve: single GPU; dense arrays up to kDirectMax DoFs (FP64 LU up to kDirectSmall, FP32 above), band
+  // storage beyond or when asked (coarse_direct 2)
   {
     const int64_t nco = mg.lev.back()->n_dofs;
     const int want = p->coarse_direct;
-    if (want > 0 && (mg.boxed || nco > kDirectMax))
-      return set_err(GLS_EINVAL, "mg: direct coarse solve needs one GPU, <= %lld DoFs", (long long)kDirectMax);
+    if (want > 2) return set_err(GLS_EINVAL, "mg: coarse_direct -1, 0, 1 or 2");
+    if (want > 0 && mg.boxed) return set_err(GLS_EINVAL, "mg: direct coarse solve needs one GPU");
     mg.direct = want > 0 || (want == 0 && !mg.boxed && nco <= 2048);
+    // 1 up to kDirectMax: the dense routes; above, or 2: band storage (the callers ran band_precheck first)
     if (mg.direct) {
-      GLS_TRY(mg.coarse.init(nco));
-      GLS_TRY(mg_probe_setup(c, mg.lev.back()));
+      const bool band = band_route_wanted(p, mg.lev.back());
+      const int rc = mg_coarse_setup("mg", c, mg.lev.back(), band);
+      // the exact byte check needs the probing ILU, attached after the detach: its refusal leaves nothing half
+      // attached (the smoother ILUs and Vanka maps put on the levels above go again; the message stays)
+      if (rc < 0 && band) (void)gls_mg_detach(c);
+      GLS_TRY(rc);
     }
   }
   mg.on = true;
@@ -794,6 +861,7 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
   if (c->dim != 3 || c->k > 2 || c->k != c->kp) return set_err(GLS_EINVAL, "mg: 3D Q1-Q1 / Q2-Q2 only");
   if (c->hang.on) return set_err(GLS_EINVAL, "mg: not with hanging-node constraints");
   if (c->map_degree > 0) return set_err(GLS_EINVAL, "mg: nested hyper_cube levels only (not mapped cells)");
+  GLS_TRY(band_precheck("mg", c, p, p->levels[p->n_levels - 1]));  // refused before anything is detached
   GLS_TRY(gls_mg_detach(c));  // a previous attach's levels / smoother ILUs
   auto &mg = c->mg;
   mg.boxed = c->dist.on;
@@ -889,6 +957,7 @@ int gls_mg_attach_transfers(gls_ctx *c, const gls_mg_params *p, const int64_t *c
   GLS_TRY(check_ctx(c));
   if (!p || p->n_levels < 2 || !p->levels || p->levels[0] != c) return set_err(GLS_EINVAL, "mg: levels[0] must be ctx");
   if (!p_off || !p_col || !p_w || !inject) return set_err(GLS_EINVAL, "mg: transfer arrays missing");
+  GLS_TRY(band_precheck("mg", c, p, p->levels[p->n_levels - 1]));  // refused before anything is built or detached
   if (p->smoother == 3) {  // refused before anything is detached: the context keeps what it had
     for (int l = 0; l + 1 < p->n_levels; ++l) {
       if (!p->levels[l]) return set_err(GLS_EINVAL, "mg level %d: null", l);
@@ -1107,8 +1176,24 @@ int gls_mg_attach_replica(gls_ctx *c, const gls_mg_params *p, gls_ctx *replica, 
   return GLS_OK;
 }
 
+int gls_mg_coarse_info(gls_ctx *c, int64_t *n, int *storage, int64_t *bl, int64_t *bu, int64_t *nb, int64_t *bytes) {
+  GLS_TRY(check_ctx(c));
+  const auto &cs = c->mg.coarse;
+  const bool on = c->mg.on && c->mg.direct, band = on && cs.band_store;
+  if (n) *n = on ? cs.n : 0;
+  if (storage) *storage = band ? 1 : 0;
+  if (bl) *bl = band ? cs.blu.L.bl : -1;
+  if (bu) *bu = band ? cs.blu.L.bu : -1;
+  if (nb) *nb = band ? cs.blu.L.nb : -1;
+  if (bytes) *bytes = !on ? 0 : band ? (int64_t)cs.blu.bytes() : (int64_t)(cs.probe.n * sizeof(double) + cs.probe32.n * sizeof(float));
+  return GLS_OK;
+}
+
 int gls_mg_detach(gls_ctx *c) {
   GLS_TRY(check_ctx(c));
+  // a coarse factorization in flight ends first: on the band route its check reads the probing ILU's CSR, which
+  // belongs to the coarsest level's context and is released just below
+  c->mg.coarse.side.reset();
   for (auto *g : c->mg.lev) g->smooth_f32 = g->smooth_oseen = false;
   // the ILU(0) smoothers the attach put on the levels (level 0 is this context) go with the multigrid, so
   // the preconditioner falls back to Jacobi (gls_native.h) and not to a leftover smoother ILU

@@ -58,6 +58,76 @@ int CoarseSolve::init(int64_t n_) {
   return GLS_OK;
 }
 
+// ---- the band route: BandLU (gls_band_lu.cpp) does the work; here its place in the preparation's lifetime rules
+int CoarseSolve::init_band(int64_t n_, int64_t block) {
+  n = n_;
+  BandLayout L;
+  if (const char *why = band_layout(n, band.bl, band.bu, block, &L))
+    return set_err(GLS_EINVAL, "mg: coarse band storage: %s", why);
+  GLS_TRY(blu.init(L));
+  GLS_TRY(tmp.alloc((size_t)n));
+  if (!blas) {
+    rocblas_handle h = nullptr;
+    if (rocblas_create_handle(&h) != kOk) return set_err(GLS_EHIP, "rocblas_create_handle failed");
+    blas.reset(h);
+  }
+  rocblas_set_pointer_mode(blas.get(), rocblas_pointer_mode_host);
+  band_store = true;
+  if (verbose_on())
+    std::printf("mg: coarse FP32 LU in band storage n=%lld bl=%lld bu=%lld nb=%lld blocks=%lld bytes=%lld\n", (long long)n,
+                (long long)L.bl, (long long)L.bu, (long long)L.nb, (long long)L.n_blocks, (long long)blu.bytes());
+  return GLS_OK;
+}
+
+int CoarseSolve::factor_band(hipStream_t s0, const int64_t *rowp, const int32_t *col, const double *val, int64_t pin,
+                             Clock::time_point t0) {
+  ok = lu = lu32 = false;
+  if (pin >= n) return set_err(GLS_EINVAL, "mg: coarsest level without pressure DoFs");
+  pin_dof = pin;
+  banded = true;
+  GLS_TRY(blu.fill(s0, rowp, col, val, band.pin));
+  HIP_TRY(side.ensure());
+  hipStream_t s = side.s;
+  HIP_TRY(hipEventRecord(side.e0, s0));
+  HIP_TRY(hipStreamWaitEvent(s, side.e0, 0));
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  side.join();
+  side.rc = 0;
+  auto *m = this;
+  const bool verbose = verbose_on();
+  side.worker = std::thread([m, s, dev, verbose]() {
+    const auto h0 = Clock::now();
+    int &rc = m->side.rc;
+    if (hipSetDevice(dev) != hipSuccess) rc = 1;
+    else rc = m->blu.factor(m->blas.get(), s);
+    if (verbose) std::printf("mg: the band FP32 LU returned to its worker thread after %.2f ms\n", ms(h0, Clock::now()));
+    if (!rc && hipEventRecord(m->side.e1, s) != hipSuccess) rc = 5;
+  });
+  pending = true;
+  if (verbose) {
+    (void)hipStreamSynchronize(s0);
+    std::printf("mg: coarse FP32 band LU n=%lld queued on the side stream at %.2f ms\n", (long long)n, ms(t0, Clock::now()));
+  }
+  ok = true;
+  return GLS_OK;
+}
+
+// no pivoted route in band storage (an explicit inverse is n^2): a failed check clears ok and is an error, so the
+// caller prepares again and no NaN reaches a V-cycle
+int CoarseSolve::finish_band() {
+  double r = INFINITY;
+  GLS_TRY(blu.read_check(side.s, &r));
+  lu32_refine = r >= 1e-2 && r < 0.5;
+  if (verbose_on())
+    std::printf("mg: coarse FP32 band LU n=%lld, check |A x - 1| / |1| = %.2e%s\n", (long long)n, r,
+                lu32_refine ? ", applied with one refinement step" : "");
+  if (r < 0.5) return GLS_OK;
+  ok = false;
+  return set_err(GLS_EINVAL, "coarse band LU failed its check: |A x - 1| / |1| = %.3e (n %lld; band storage has no pivoted "
+                             "route)", r, (long long)n);
+}
+
 // A <- A^-1 on s: getrf (pivoted or not), info read back, getri, info read back (one host wait each). *inf: the
 // failing step's info, 0 when A holds the inverse; getri is skipped after a failed getrf
 template <class T>
@@ -279,6 +349,7 @@ int CoarseSolve::finish(hipStream_t s) {
     ok = lu32 = false;
     return set_err(GLS_EHIP, "coarse FP32 LU on the side stream failed (step %d)", side.rc);
   }
+  if (band_store) return finish_band();
   // info is what the LAST sgetrf_npvt call left: in the banded loop every column block overwrites it (and counts
   // pivots from its own first column), so a zero pivot in an earlier block is not seen here. inf == 0 only screens;
   // the residual check below decides (a vanished pivot leaves it O(1) or non-finite)
@@ -311,6 +382,13 @@ int CoarseSolve::finish(hipStream_t s) {
 
 int CoarseSolve::solve(hipStream_t s, const double *b, double *x, const int32_t *perm) {
   const rocblas_int N = (rocblas_int)n;
+  if (band_store) {  // the band-storage factor, in the CSR's Cuthill-McKee order
+    HIP_TRY(gls::vec_permute(tmp.p, b, perm, n, 0, s));
+    GLS_TRY(blu.solve(s, tmp.p, tmp.p, lu32_refine));
+    HIP_TRY(gls::vec_permute(x, tmp.p, perm, n, 1, s));
+    HIP_TRY(hipMemsetAsync(x + pin_dof, 0, sizeof(double), s));  // pinned: no correction
+    return GLS_OK;
+  }
   if (lu32) {  // the FP32 factor / inverse, in the matrix's order (banded: the CSR's Cuthill-McKee order)
     const double *bb = b;
     double *xx = x;

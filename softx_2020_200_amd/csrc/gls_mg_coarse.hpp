@@ -2,6 +2,8 @@
 // the dense matrix, its factors, the scratch vectors, the rocBLAS handle and the side stream with its worker thread;
 // it sees an n x n column-major array (and, for a banded matrix, its bandwidths and permutation), never a context:
 // the multigrid (gls_mg.cpp) probes the level's Jacobian into matrix() and calls factor / finish / solve.
+// Above kDirectMax unknowns (or when asked) the n x n arrays give way to band storage filled from the probed CSR
+// (init_band / factor_band, gls_band_lu.hpp); finish and solve are the same calls.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +17,7 @@
 
 #include <rocblas/rocblas.h>
 
+#include "gls_band_lu.hpp"
 #include "gls_devbuf.hpp"
 
 namespace gls_impl {
@@ -63,6 +66,11 @@ struct CoarseSolve {
   int64_t pin_dof = 0;   // the pinned unknown (first pressure DoF) and its row in the matrix's order
   int64_t pin_row() const { return banded ? band.pin : pin_dof; }
   DevBuf<double> rel;    // |A x - 1| of the FP32 check (device pointer mode)
+  // the band route (init_band): the FP32 matrix in block-tridiagonal storage filled from the probing ILU's CSR
+  // (gls_band_lu.hpp), for levels whose n x n arrays do not fit -- probe / probe32 stay empty. Factored on the side
+  // stream by the worker like the dense FP32 route, checked and refined against the FP64 CSR; no pivoted fallback
+  bool band_store = false;
+  BandLU blu;
   Clock::time_point t_getrf;  // when invert()'s last getrf had returned its info (verbose timings)
   // the FP32 unpivoted factorization and its check run on a stream of their own, overlapping the finer levels'
   // ILU setup and first smoothing on the context stream; the first coarse solve waits for them (finish).
@@ -121,6 +129,11 @@ struct CoarseSolve {
   // the one allocation routine (both attach paths): the FP64 matrix and pivots, the FP32 copies above kDirectSmall,
   // the Gauss-Jordan buffer whenever GLS_MG_COARSE_SOLVER is set, the rocBLAS handle
   int init(int64_t n);
+  // the band route's allocations instead: the panels for the bandwidths in band (set by the prober), no dense array
+  int init_band(int64_t n, int64_t block);
+  // ... and its factorization: the panels filled from the CSR (device, in the band's order, unchanged until the next
+  // preparation) on s, the block LU and its check handed to the worker
+  int factor_band(hipStream_t s, const int64_t *rowp, const int32_t *col, const double *val, int64_t pin, Clock::time_point t0);
   double *matrix() { return probe.p; }  // the prober writes the dense FP64 matrix here (column-major n x n)
   // factor the probed matrix on s with the DoF pin pinned; banded_: the matrix is in the band's order. The route by n
   // and GLS_MG_COARSE_SOLVER (gj | lu | lu_npvt): up to kDirectSmall in place and checked, above rounded to FP32 and
@@ -138,6 +151,7 @@ struct CoarseSolve {
   int inverse_check(hipStream_t s, bool *good);
   int factor_f64(hipStream_t s, const char *route, Clock::time_point t0, Clock::time_point t1);
   int start_f32(hipStream_t s);
+  int finish_band();
 };
 
 }  // namespace gls_impl

@@ -15,6 +15,7 @@
 // Multi-GPU: each rank works on the box sub-lattice its cells span (box gather / scatter through
 // a box -> local node map); nested partitions keep the coarse box the fine box's every-second node.
 #include "gls_launch.hpp"
+#include "gls_lu_step.hpp"
 
 namespace gls {
 
@@ -506,152 +507,12 @@ hipError_t mg_dense_apply(const double *aug, int n, const double *b, double *x, 
   return hipGetLastError();
 }
 
-// ---- dense LU solves of the coarsest level (FP32 factor of rocSOLVER getrf_npvt: column-major, lda = n, unit
-// lower L below the diagonal, U on and above it); x overwritten. Block-column steps of kLuB rows: step k has the
-// block k solution final; its workgroup 0 applies that block's column to the rows of the next block and solves the
-// next diagonal block in LDS (one column at a time), the other workgroups apply it to the rows beyond. 2 n / kLuB
-// launches per solve against rocBLAS trsv's 62 ms at n = 25000 (profiles/r06_lu25k.txt).
-constexpr int kLuB = 128;
-namespace {
-// Step k (k < 0: the first diagonal block alone, block 0 forward / the last block backward): workgroup 0 applies
-// block column k to the next diagonal block's rows and solves that diagonal block, the others apply block column k
-// to the rows beyond. A launch is bound by memory latency, so every global load of it is issued in ONE round before
-// anything waits: the right-hand side, block k's solution, and the two 128 x 128 blocks workgroup 0 reads (its rows
-// of block column k, the diagonal block), 16-byte loads along the columns, 16 + 16 per thread of 256, staged in LDS.
-// (Rounds of dependent loads cost ~2 us each: 128 rounds of one load per thread, 72 / 113 us per forward / backward
-// launch; rounds of 32, 21 us; profiles/r06_lu_solve_ab.txt.) The diagonal block is then solved by two wavefronts
-// in turn, one column at a time with the column's value broadcast from its lane by v_readlane (no workgroup
-// barrier in the sequential part; one hands the first half to the second).
-constexpr int kLuT = 256;
-template <bool LOWER, bool VEC>
-__global__ void __launch_bounds__(kLuT) k_lu_step(const float *__restrict__ A, int n, float *__restrict__ x, int k,
-                                                  int rlo) {  // rlo: backward, the first row block the others update
-  __shared__ float xk[kLuB], xb[kLuB], rd[kLuB], part[2][kLuB];
-  __shared__ float D[kLuB][kLuB + 1], C[kLuB][kLuB + 1];
-  const int t = threadIdx.x, nb = (n + kLuB - 1) / kLuB;
-  const bool first = k < 0, diag = blockIdx.x == 0;
-  const int j0 = first ? 0 : k * kLuB, nj = first ? 1 : min(kLuB, n - j0);
-  const int kn = first ? (LOWER ? 0 : nb - 1) : (LOWER ? k + 1 : k - 1);  // the diagonal block solved here
-  const int r0 = kn * kLuB, nr = min(kLuB, n - r0);
-  const int rb = diag ? r0 : LOWER ? (k + 1 + (int)blockIdx.x) * kLuB : (rlo + (int)blockIdx.x - 1) * kLuB;  // row block
-  const int row = t & (kLuB - 1), half = t >> 7;
-  const int i = rb + row;
-  const bool live = half == 0 && (diag ? row < nr : LOWER ? i < n : i < kn * kLuB);
-  // the round of loads
-  const float xi = x[min(i, n - 1)];
-  const float xkt = first ? 0.f : x[j0 + min(row, nj - 1)];
-  const int r4 = t & 31, cq = t >> 5;  // this thread's 4-row slot and column (of 8) in each 16-byte load round
-  auto ld = [&](int rbase, int cb, int ncol, int q) {
-    const int r = rbase + 4 * r4;
-    const int64_t c = (int64_t)(cb + min(q * 8 + cq, ncol - 1)) * n;
-    if (VEC && r + 3 < n) return *reinterpret_cast<const float4 *>(A + r + c);
-    return make_float4(A[min(r, n - 1) + c], A[min(r + 1, n - 1) + c], A[min(r + 2, n - 1) + c], A[min(r + 3, n - 1) + c]);
-  };
-  float4 qc[16], qd[16];
-  if (!first) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) qc[q] = ld(rb, j0, nj, q);
-  }
-  if (diag) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) qd[q] = ld(r0, r0, nr, q);
-  }
-  if (half == 0) xk[row] = row < nj ? xkt : 0.f;
-  if (!first) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int c = q * 8 + cq;
-      C[4 * r4][c] = qc[q].x, C[4 * r4 + 1][c] = qc[q].y, C[4 * r4 + 2][c] = qc[q].z, C[4 * r4 + 3][c] = qc[q].w;
-    }
-  }
-  if (diag) {  // outside the block: identity
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int c = q * 8 + cq;
-      const float e[4] = {qd[q].x, qd[q].y, qd[q].z, qd[q].w};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int rr = 4 * r4 + u;
-        D[rr][c] = rr < nr && c < nr ? e[u] : (rr == c ? 1.f : 0.f);
-      }
-    }
-  }
-  __syncthreads();
-  float v = xi;
-  if (!first) {  // the block column's product, two threads per row (halves of the columns)
-    float sacc = 0.f;
-#pragma unroll 16
-    for (int c = 0; c < 64; ++c) sacc += C[row][64 * half + c] * xk[64 * half + c];  // (xk = 0 past the block)
-    part[half][row] = sacc;
-    __syncthreads();
-    v = xi - part[0][row] - part[1][row];
-  }
-  if (!diag) {
-    if (live) x[i] = v;
-    return;
-  }
-  const int lane = t & 63, w = t >> 6;
-  if (!LOWER && half == 0) {  // (read back by the writing wavefront only)
-    rd[t] = 1.f / D[t][t];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-  auto bcast = [](float q, int c) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q), c)); };
-  auto tri = [&](int cb) {  // the wavefront's own 64 x 64 triangle
-    if (LOWER) {
-#pragma unroll
-      for (int c = 0; c < 64; ++c) {
-        const float xc = bcast(v, c), dv = D[t][cb + c];
-        v = __builtin_fmaf(lane > c ? -dv : 0.f, xc, v);
-      }
-    } else {
-      float xs = 0.f;
-#pragma unroll
-      for (int c = 63; c >= 0; --c) {
-        const float xc = bcast(v, c) * rd[cb + c], dv = D[t][cb + c];
-        xs = lane == c ? xc : xs;
-        v = __builtin_fmaf(lane < c ? -dv : 0.f, xc, v);
-      }
-      v = xs;
-    }
-  };
-  const int wf = LOWER ? 0 : 1;  // the wavefront solved first
-  if (w == wf) {
-    tri(64 * wf);
-    xb[t] = v;
-  }
-  __syncthreads();
-  if (w == 1 - wf) {
-    const int cb = 64 * wf;
-#pragma unroll 16
-    for (int c = 0; c < 64; ++c) v -= D[t][cb + c] * xb[cb + c];
-    tri(64 * w);
-  }
-  if (live) x[i] = v;
-}
-// bl / bu >= 0: lower / upper bandwidths -- a step updates only the row blocks its block column reaches
-template <bool VEC>
-void lu_solve(const float *LU, int n, float *x, hipStream_t s, int bl, int bu) {
-  const int nb = (n + kLuB - 1) / kLuB;
-  hipLaunchKernelGGL((k_lu_step<true, VEC>), dim3(1), dim3(kLuT), 0, s, LU, n, x, -1, 0);
-  for (int k = 0; k + 1 < nb; ++k) {
-    const int end = bl < 0 ? n : std::min(n, (k + 1) * kLuB + bl);  // rows below reached by block column k
-    const int rest = end - (k + 2) * kLuB;
-    hipLaunchKernelGGL((k_lu_step<true, VEC>), dim3(1 + (rest > 0 ? (rest + kLuB - 1) / kLuB : 0)), dim3(kLuT), 0, s, LU,
-                       n, x, k, 0);
-  }
-  hipLaunchKernelGGL((k_lu_step<false, VEC>), dim3(1), dim3(kLuT), 0, s, LU, n, x, -1, 0);
-  for (int k = nb - 1; k >= 1; --k) {
-    const int rlo = bu < 0 ? 0 : std::max(0, k * kLuB - bu) / kLuB;  // rows above reached by block column k
-    const int nblk = std::max(0, (k - 1) - rlo);
-    hipLaunchKernelGGL((k_lu_step<false, VEC>), dim3(1 + nblk), dim3(kLuT), 0, s, LU, n, x, k, rlo);
-  }
-}
-}  // namespace
+// ---- dense LU solves of the coarsest level (FP32 factor of rocSOLVER getrf_npvt: column-major, lda = n): the
+// substitution of gls_lu_step.hpp on the dense addressing
 hipError_t dense_lu_solve_f32(const float *LU, int n, float *x, hipStream_t s, int bl, int bu) {
   if (n <= 0) return hipSuccess;
-  if (n % 4 == 0 && reinterpret_cast<uintptr_t>(LU) % 16 == 0) lu_solve<true>(LU, n, x, s, bl, bu);
-  else lu_solve<false>(LU, n, x, s, bl, bu);
+  if (n % 4 == 0 && reinterpret_cast<uintptr_t>(LU) % 16 == 0) lu_solve_steps<true>(LU, LuDense{n}, x, s, bl, bu);
+  else lu_solve_steps<false>(LU, LuDense{n}, x, s, bl, bu);
   return hipGetLastError();
 }
 

@@ -55,6 +55,7 @@ EXPORTS = [
     "gls_output_plan_create", "gls_output_plan_destroy", "gls_output_fields", "gls_vtu_write_device",
     "gls_vanka_sizes", "gls_vanka_element_matrices", "gls_vanka_patch_inverses", "gls_vanka_sweep", "gls_vanka_detach",
     "gls_vanka_maps",
+    "gls_mg_coarse_info", "gls_band_lu_layout", "gls_band_lu_create", "gls_band_lu_solve", "gls_band_lu_info", "gls_band_lu_destroy",
 ]
 
 
@@ -211,6 +212,12 @@ def load():
     L.gls_vanka_detach.argtypes = [vp]
     L.gls_vanka_maps.argtypes = [C.c_int] * 3 + [i64] * 3 + [C.POINTER(C.c_int32)] * 4 + [C.POINTER(i64), C.POINTER(C.c_int32), i64,
                                  C.POINTER(i64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i64, C.POINTER(i64), C.POINTER(i64)]
+    L.gls_mg_coarse_info.argtypes = [vp, C.POINTER(i64), C.POINTER(C.c_int)] + [C.POINTER(i64)] * 4
+    L.gls_band_lu_layout.argtypes = [i64] * 4 + [C.POINTER(i64)] * 3
+    L.gls_band_lu_create.argtypes = [i64, C.POINTER(i64), C.POINTER(C.c_int32), d, i64, i64, C.POINTER(vp)]
+    L.gls_band_lu_solve.argtypes = [vp, vp, vp, C.c_int]
+    L.gls_band_lu_info.argtypes = [vp] + [C.POINTER(i64)] * 4 + [d]
+    L.gls_band_lu_destroy.argtypes = [vp]
     L.gls_mg_residual_restrict.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
     L.gls_mg_prolong_smooth.argtypes = [vp, C.c_int, vp, vp, vp, C.c_double, C.POINTER(C.c_int)]
     P64 = C.POINTER(i64)
@@ -926,6 +933,15 @@ class GLSContext:
         check(self.L.gls_mg_attach_transfers(self.h, C.byref(p), offs, cols, ws, injs), "gls_mg_attach_transfers")
         self._mg_levels = levels
 
+    def mg_coarse_info(self):
+        """{n, storage ("dense" | "band"), bl, bu, nb, bytes} of the attached hierarchy's direct coarse solve
+        (gls_mg_coarse_info); n = 0 without one."""
+        v = [C.c_int64(0) for _ in range(5)]
+        st = C.c_int(0)
+        check(self.L.gls_mg_coarse_info(self.h, C.byref(v[0]), C.byref(st), *[C.byref(a) for a in v[1:]]), "gls_mg_coarse_info")
+        return {"n": v[0].value, "storage": "band" if st.value else "dense", "bl": v[1].value, "bu": v[2].value,
+                "nb": v[3].value, "bytes": v[4].value}
+
     def attach_multigrid_replica(self, replica, p_off, p_col, p_w, inject_local, pre_smooth=2, post_smooth=2,
                                  omega=0.6, smoother="jacobi", coarse_direct=0):
         """The refinement-hierarchy V-cycle across ranks (gls_mg_attach_replica): this distributed fine
@@ -1605,3 +1621,49 @@ def vanka_maps(dim, k, kp, cell_vnodes, cell_pnodes, n_vnodes, n_pnodes):
                            out["ov_i"].ctypes.data_as(pu8), out["ov_j"].ctypes.data_as(pu8), nov.value, C.byref(npair),
                            C.byref(nov)), "gls_vanka_maps")
     return out
+
+
+def band_lu_layout(n, bl, bu, block=0):
+    """(nb, n_blocks, n_floats) of the band-storage LU's panels (gls_band_lu_layout; host only, no GPU)."""
+    nb, nblk, nfl = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(load().gls_band_lu_layout(n, bl, bu, block, C.byref(nb), C.byref(nblk), C.byref(nfl)), "gls_band_lu_layout")
+    return nb.value, nblk.value, nfl.value
+
+
+class BandLU:
+    """The band-storage FP32 LU of a host CSR matrix in FP64 (gls_band_lu_create): rowp (n + 1), col, val; row and
+    column `pin` replaced by identity (pin < 0: none); block: the block width (0: by the band)."""
+
+    def __init__(self, rowp, col, val, pin=-1, block=0):
+        self.L = load()
+        rp, cl = np.ascontiguousarray(rowp, np.int64), np.ascontiguousarray(col, np.int32)
+        vl = np.ascontiguousarray(val, np.float64)
+        self.n = len(rp) - 1
+        self.h = C.c_void_p()
+        check(self.L.gls_band_lu_create(self.n, rp.ctypes.data_as(C.POINTER(C.c_int64)), cl.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        _dp(vl), pin, block, C.byref(self.h)), "gls_band_lu_create")
+
+    def solve(self, b, refine=False):
+        """x = A^-1 b (float64 CUDA tensors of n), x[pin] = 0; refine: one refinement step against the FP64 CSR."""
+        import torch
+        x = torch.empty_like(b)
+        check(self.L.gls_band_lu_solve(self.h, _ptr(b), _ptr(x), 1 if refine else 0), "gls_band_lu_solve")
+        return x
+
+    def info(self):
+        """{bl, bu, nb, bytes, check}: the CSR's bandwidths, the block width, the panels' bytes, |A x - 1| / |1|."""
+        v = [C.c_int64(0) for _ in range(4)]
+        chk = C.c_double(0.0)
+        check(self.L.gls_band_lu_info(self.h, *[C.byref(a) for a in v], C.byref(chk)), "gls_band_lu_info")
+        return {"bl": v[0].value, "bu": v[1].value, "nb": v[2].value, "bytes": v[3].value, "check": chk.value}
+
+    def close(self):
+        if self.h:
+            self.L.gls_band_lu_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

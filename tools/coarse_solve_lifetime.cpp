@@ -29,11 +29,14 @@ rocblas_status rocblas_destroy_handle(rocblas_handle) { return rocblas_status_su
 
 static void start_worker(gls_impl::CoarseSolve &cs) {
   if (cs.rel.alloc(1) != GLS_OK || cs.chk32.alloc(64) != GLS_OK) std::exit(2);
+  // the band route's buffers (BandLU, a member declared before Side): its panels, scratch and check result
+  if (cs.blu.panels.alloc(64) != GLS_OK || cs.blu.work.alloc(64) != GLS_OK || cs.blu.rel.alloc(1) != GLS_OK) std::exit(2);
   // (the pointers as the worker's queued device work holds them)
-  cs.side.worker = std::thread([chk = cs.chk32.p, n = cs.chk32.n, rel = cs.rel.p]() {
+  cs.side.worker = std::thread([chk = cs.chk32.p, n = cs.chk32.n, rel = cs.rel.p, pan = cs.blu.panels.p, wrk = cs.blu.work.p,
+                                brel = cs.blu.rel.p]() {
     std::this_thread::sleep_for(std::chrono::milliseconds(200));
-    for (size_t i = 0; i < n; ++i) chk[i] = 1.0;
-    *rel = 64.0;  // what rocblas_dnrm2 writes in device pointer mode
+    for (size_t i = 0; i < n; ++i) chk[i] = 1.0, pan[i] = 1.f, wrk[i] = 1.0;
+    *rel = *brel = 64.0;  // what rocblas_dnrm2 writes in device pointer mode
   });
 }
 
