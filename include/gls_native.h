@@ -267,6 +267,19 @@ typedef struct {
                                                  Jacobian either way */
 } gls_mg_params;
 int gls_mg_attach(gls_ctx *ctx, const gls_mg_params *prm);
+/* The same hierarchy on hyper_cubes with periodic directions (bit d of periodic_mask: direction d is periodic;
+ * mask 0 is gls_mg_attach). Level l has n_l = cbrt(n_cells) cells per direction, n_{l+1} = n_l / 2, and its Qk node
+ * lattice has k n_l nodes on a periodic axis and k n_l + 1 on the others, so nf = 2 nc across a periodic axis and
+ * nf = 2 nc - 1 elsewhere. Every level's node numbering is checked cell by cell against the lexicographic wrapped
+ * lattice of gls_mesh_hyper_cube(..., periodic_mask, ...) (any cell order). The interpolation is the open lattice's
+ * without the clamp at the far end: fine node i lies in coarse cell floor(i / (2k)) and coarse node (cc k + q) mod nc
+ * carries the weight; restriction is the transpose (Q2: every coarse vertex node has the full five-tap row). The
+ * transfers run the two-pass kernels, which wrap at the seam where they load; the restriction / prolongation fused
+ * into the smoother launches (gls_mg_residual_restrict, gls_mg_prolong_smooth) are the open cube's, so periodic
+ * levels report fused = 0. GLS_EINVAL with a message, before anything is detached (the context keeps the hierarchy
+ * it had): a level that is not that lattice (the level is named), a distributed context or level with a non-zero
+ * mask, a level with fewer than 2 cells per direction, and whatever gls_mg_attach refuses. One GPU. */
+int gls_mg_attach_periodic(gls_ctx *ctx, const gls_mg_params *prm, int periodic_mask);
 /* The same V-cycle on a general level hierarchy with the caller's grid transfers: levels of an adaptive
  * (octree) mesh with hanging-node constraints (gls_set_hanging before attaching), e.g. the global
  * coarsening gls_octree_coarsen_to / gls_octree_mg_transfer builds. For l = 0 .. n_levels-2:

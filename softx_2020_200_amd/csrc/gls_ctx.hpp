@@ -281,6 +281,9 @@ struct gls_ctx {
       // Q2: every axis' taps are the brick-local 5 <-> 3 table the pencil J.v's in-kernel restriction uses
       // (fine nodes 4 c .. 4 c + 4 from coarse nodes 2 c .. 2 c + 2: 1 | 3/8 3/4 -1/8 | 1 | -1/8 3/4 3/8 | 1)
       bool q2_brick = false;
+      // a periodic axis (gls_mg_attach_periodic): its taps are stored unwrapped at the seam and the two-pass kernels
+      // take their input modulo the lattice; never q2_brick, never the one-pass gather
+      bool wrap = false;
     };
     std::vector<std::unique_ptr<Taps>> taps;
     // general hierarchies (gls_mg_attach_transfers): per level pair the prolongation P (fine rows), the

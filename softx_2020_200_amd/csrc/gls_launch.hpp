@@ -288,7 +288,8 @@ hipError_t mg_transfer3d(const double *in, double *out, const int nin[3], const 
 // larger) doubles. tile_fits: host check that a per-axis tap table (axis 0/1) fits the kernel's tiles.
 hipError_t mg_transfer_2pass(const double *in, double *out, const int nin[3], const int nout[3], int restrict_,
                              const int32_t *const taps[3], const double *const w[3], const int32_t *const cnt[3],
-                             double *work, hipStream_t s, int add = 0);  // add (prolongation): out += P in
+                             double *work, hipStream_t s, int add = 0, int wrap = 0);  // add (prolongation): out += P in
+// wrap: a lattice with periodic axes, whose tap tables hold unwrapped indices at the seam (gls_mg_attach_periodic)
 int mg_transfer_tile_fits(int restrict_, int axis, int n_out, const int32_t *taps, const int32_t *cnt);
 hipError_t mg_box_gather(const double *loc, double *box, const int32_t *map, int64_t nbox, int64_t nvl,
                          int64_t n_owned, hipStream_t s);  // n_owned < 0: all nodes

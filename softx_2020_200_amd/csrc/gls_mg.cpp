@@ -341,7 +341,7 @@ int mg_restrict(gls_ctx *c, int l, const double *y, double *bc) {
     const double *tw[3] = {T.rw[0].p, T.rw[1].p, T.rw[2].p};
     if (T.two_pass)
       HIP_TRY(gls::mg_transfer_2pass(yb, mg_box_target(c, l + 1, bc), mg.dims[l].data(), mg.dims[l + 1].data(), 1, ti,
-                                     tw, tc, mg.xwork.p, s));
+                                     tw, tc, mg.xwork.p, s, 0, T.wrap ? 1 : 0));
     else
       HIP_TRY(gls::mg_transfer3d(yb, mg_box_target(c, l + 1, bc), mg.dims[l].data(), mg.dims[l + 1].data(), ti, tw,
                                  tc, s));
@@ -375,7 +375,7 @@ int mg_prolong(gls_ctx *c, int l, double *xc, double *y, bool add = false) {
     const double *tw[3] = {T.pw[0].p, T.pw[1].p, T.pw[2].p};
     if (T.two_pass)
       HIP_TRY(gls::mg_transfer_2pass(xb, mg_box_target(c, l, y), mg.dims[l + 1].data(), mg.dims[l].data(), 0, ti, tw,
-                                     tc, mg.xwork.p, s, add ? 1 : 0));
+                                     tc, mg.xwork.p, s, add ? 1 : 0, T.wrap ? 1 : 0));
     else if (add)
       return set_err(GLS_EINVAL, "mg_prolong: accumulate needs the two-pass transfer");
     else
@@ -852,7 +852,43 @@ static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
   return GLS_OK;
 }
 
-int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
+namespace {
+// nodes per direction of the Qk lattice of an n-cell hyper_cube: a periodic axis has no node of its own at the far face
+std::array<int, 3> wrapped_dims(int n, int K, int mask) {
+  std::array<int, 3> d;
+  for (int a = 0; a < 3; ++a) d[a] = K * n + (((mask >> a) & 1) ? 0 : 1);
+  return d;
+}
+// level g's cells against the lexicographic wrapped lattice dm (the numbering of gls_mesh_hyper_cube with this mask),
+// cell by cell and in any cell order: a cell's first node fixes its origin, a multiple of K per axis, every other node
+// follows modulo the lattice, and no origin is taken twice. nullptr, or what differs
+const char *wrapped_lattice_mismatch(const gls_ctx *g, int n, int K, const std::array<int, 3> &dm, std::vector<int32_t> &cv) {
+  const int K1 = K + 1, N3 = K1 * K1 * K1;
+  if ((int64_t)n * n * n != g->n_cells || (int64_t)dm[0] * dm[1] * dm[2] != g->n_vnodes) return "cell or node count";
+  if (g->cell_vnodes.n != (size_t)g->n_cells * N3) return "cell node array";
+  cv.resize(g->cell_vnodes.n);
+  if (hipMemcpy(cv.data(), g->cell_vnodes.p, sizeof(int32_t) * cv.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return "cell node array could not be read";
+  std::vector<uint8_t> seen((size_t)g->n_cells, 0);
+  for (int64_t cl = 0; cl < g->n_cells; ++cl) {
+    const int32_t *v = cv.data() + (size_t)cl * N3;
+    if (v[0] < 0 || v[0] >= g->n_vnodes) return "node out of range";
+    const int o[3] = {v[0] % dm[0], (v[0] / dm[0]) % dm[1], v[0] / (dm[0] * dm[1])};
+    for (int a = 0; a < 3; ++a)
+      if (o[a] % K != 0 || o[a] / K >= n) return "cell origin off the lattice";
+    uint8_t &sn = seen[(size_t)(((int64_t)(o[2] / K) * n + o[1] / K) * n + o[0] / K)];
+    if (sn) return "two cells at one origin";
+    sn = 1;
+    for (int e = 1; e < N3; ++e) {
+      const int64_t x = (o[0] + e % K1) % dm[0], y = (o[1] + (e / K1) % K1) % dm[1], z = (o[2] + e / (K1 * K1)) % dm[2];
+      if (v[e] != (int32_t)(x + dm[0] * (y + dm[1] * z))) return "cell nodes";
+    }
+  }
+  return nullptr;
+}
+
+// gls_mg_attach (mask 0) and gls_mg_attach_periodic
+int mg_attach_nested(gls_ctx *c, const gls_mg_params *p, int mask) {
   GLS_TRY(check_ctx(c));
   if (!p || p->n_levels < 2 || !p->levels || p->levels[0] != c) return set_err(GLS_EINVAL, "mg: levels[0] must be ctx");
   if (p->smoother == 3)
@@ -861,6 +897,31 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
   if (c->dim != 3 || c->k > 2 || c->k != c->kp) return set_err(GLS_EINVAL, "mg: 3D Q1-Q1 / Q2-Q2 only");
   if (c->hang.on) return set_err(GLS_EINVAL, "mg: not with hanging-node constraints");
   if (c->map_degree > 0) return set_err(GLS_EINVAL, "mg: nested hyper_cube levels only (not mapped cells)");
+  // periodic lattices: every level is checked here, before anything is detached (the context keeps what it had)
+  std::vector<std::array<int, 3>> pdims;
+  if (mask) {
+    if (mask < 0 || mask > 7) return set_err(GLS_EINVAL, "mg: periodic_mask has bits 0 - 2 (x, y, z)");
+    if (c->dist.on)
+      return set_err(GLS_EINVAL, "mg: periodic nested levels run on one rank (periodic_mask %d on a distributed context)", mask);
+    std::vector<int32_t> cv;
+    int nprev = 0;
+    for (int l = 0; l < p->n_levels; ++l) {
+      const gls_ctx *g = p->levels[l];
+      if (!g || g->dim != 3 || g->k != c->k || g->kp != c->kp)
+        return set_err(GLS_EINVAL, "mg level %d: order differs from level 0", l);
+      if (g->dist.on) return set_err(GLS_EINVAL, "mg level %d: periodic nested levels run on one rank (the level is distributed)", l);
+      if (g->hang.on || g->map_degree > 0) return set_err(GLS_EINVAL, "mg level %d: hanging nodes or mapped cells", l);
+      const int n = (int)std::lround(std::cbrt((double)g->n_cells));
+      if (n < 2) return set_err(GLS_EINVAL, "mg level %d: a periodic direction needs at least 2 cells (it has %d)", l, n);
+      if (l > 0 && nprev != 2 * n) return set_err(GLS_EINVAL, "mg level %d not nested (%d cells per direction below %d)", l, n, nprev);
+      const auto dm = wrapped_dims(n, c->k, mask);
+      if (const char *why = wrapped_lattice_mismatch(g, n, c->k, dm, cv))
+        return set_err(GLS_EINVAL, "mg level %d: its node numbering is not the wrapped lexicographic lattice of the "
+                                   "hyper_cube with periodic mask %d (%s)", l, mask, why);
+      pdims.push_back(dm);
+      nprev = n;
+    }
+  }
   GLS_TRY(band_precheck("mg", c, p, p->levels[p->n_levels - 1]));  // refused before anything is detached
   GLS_TRY(gls_mg_detach(c));  // a previous attach's levels / smoother ILUs
   auto &mg = c->mg;
@@ -870,7 +931,9 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
     if (!g || g->dim != 3 || g->k != c->k || g->kp != c->kp || g->dist.on != mg.boxed)
       return set_err(GLS_EINVAL, "mg level %d: order / distribution differs from level 0", l);
     std::array<int, 3> dm;
-    if (mg.boxed) {
+    if (mask) {
+      dm = pdims[(size_t)l];
+    } else if (mg.boxed) {
       if (!g->lat.set) return set_err(GLS_EINVAL, "mg level %d: distributed level without gls_set_lattice", l);
       for (int a = 0; a < 3; ++a) dm[a] = g->lat.bdim[a];
       if (l > 0) {
@@ -890,22 +953,28 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
     mg.dims.push_back(dm);
   }
   // 1D transfer taps: fine lattice index i sits at x = i / (2k) coarse cells from the box origin;
-  // prolongation interpolates the coarse Qk field of the parent cell (equidistant nodes, k <= 2)
+  // prolongation interpolates the coarse Qk field of the parent cell (equidistant nodes, k <= 2).
+  // A periodic axis (nf = 2 nc): the parent cell is floor(x) without the clamp and coarse node cc k + q wraps modulo
+  // nc. The tables hold the indices unwrapped (the prolongation's nc for node 0 behind the last cell, the
+  // restriction's i - nf for the fine nodes before node 0), ascending per output, and the kernels wrap where they load.
   const int K = c->k;
   size_t xwork = 0;
   for (int l = 0; l + 1 < p->n_levels; ++l) {
     std::unique_ptr<gls_ctx::MG::Taps> T(new gls_ctx::MG::Taps);
     T->two_pass = true;
-    T->q2_brick = K == 2;
+    T->q2_brick = K == 2 && mask == 0;  // the fused transfers' closed form is the open lattice's (nf = 2 nc - 1)
+    T->wrap = mask != 0;
     xwork =std::max(xwork, (size_t)4 * mg.dims[l + 1][0] * mg.dims[l + 1][1] * mg.dims[l][2]);
     for (int a = 0; a < 3; ++a) {
+      const bool per = (mask >> a) & 1;
       const int nf = mg.dims[l][a], nc = mg.dims[l + 1][a], ncc = (nf - 1) / (2 * K);
+      if (per ? nf != 2 * nc : nf != 2 * nc - 1) return set_err(GLS_EINVAL, "mg level %d not nested (axis %d)", l + 1, a);
       std::vector<int32_t> pi((size_t)nf * 5, 0), ri((size_t)nc * 5, 0);
       std::vector<double> pw((size_t)nf * 5, 0.0), rw((size_t)nc * 5, 0.0);
       std::vector<int32_t> rn((size_t)nc, 0), pn((size_t)nf, 0);
       for (int i = 0; i < nf; ++i) {
         const double x = (double)i / (2.0 * K);
-        const int cc = std::min((int)std::floor(x), ncc - 1);
+        const int cc = per ? (int)std::floor(x) : std::min((int)std::floor(x), ncc - 1);
         const double xi = x - cc;
         int np = 0;
         for (int q = 0; q <= K; ++q) {
@@ -913,17 +982,17 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
           for (int b = 0; b <= K; ++b)
             if (b != q) L *= (xi * K - b) / (double)(q - b);
           if (L == 0.0) continue;
-          const int j = cc * K + q;
-          pi[(size_t)i * 5 + np] = j;
+          const int ju = cc * K + q, j = per ? ju % nc : ju;  // ju == nc: coarse node 0 behind the seam
+          pi[(size_t)i * 5 + np] = ju;
           pw[(size_t)i * 5 + np] = L;
           ++np;
           if (rn[(size_t)j] >= 5) return set_err(GLS_EINVAL, "mg: restriction stencil wider than 5");
-          ri[(size_t)j * 5 + rn[(size_t)j]] = i;
+          ri[(size_t)j * 5 + rn[(size_t)j]] = ju != j ? i - nf : i;
           rw[(size_t)j * 5 + rn[(size_t)j]] = L;
           ++rn[(size_t)j];
         }
         pn[(size_t)i] = np;
-        if (K == 2) {  // the closed form of the in-kernel restriction, checked tap by tap
+        if (K == 2 && !per) {  // the closed form of the in-kernel restriction, checked tap by tap
           static const double W[5][3] = {{1, 0, 0}, {0.375, 0.75, -0.125}, {0, 1, 0}, {-0.125, 0.75, 0.375}, {0, 0, 1}};
           const int m = i - 4 * cc;
           int nz = 0;
@@ -936,6 +1005,13 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
           T->q2_brick = T->q2_brick && same && nf == 2 * nc - 1;
         }
       }
+      if (per)  // the seam's rows took their taps before node 0 last: ascending order again
+        for (int j = 0; j < nc; ++j)
+          for (int e = 1; e < rn[(size_t)j]; ++e)
+            for (int f = e; f > 0 && ri[(size_t)j * 5 + f] < ri[(size_t)j * 5 + f - 1]; --f) {
+              std::swap(ri[(size_t)j * 5 + f], ri[(size_t)j * 5 + f - 1]);
+              std::swap(rw[(size_t)j * 5 + f], rw[(size_t)j * 5 + f - 1]);
+            }
       if (a < 2)
         T->two_pass = T->two_pass && gls::mg_transfer_tile_fits(0, a, nf, pi.data(), pn.data()) &&
                       gls::mg_transfer_tile_fits(1, a, nc, ri.data(), rn.data());
@@ -946,10 +1022,22 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) {
       GLS_TRY(T->pc[a].upload(pn.data(), pn.size()));
       GLS_TRY(T->rc[a].upload(rn.data(), rn.size()));
     }
+    // only the two-pass kernels wrap: the one-pass gather would read the unwrapped taps as they stand
+    if (T->wrap && !T->two_pass) {
+      (void)gls_mg_detach(c);
+      return set_err(GLS_EINVAL, "mg level %d: the periodic lattice's taps do not fit the two-pass transfer tiles", l);
+    }
     mg.taps.push_back(std::move(T));
   }
   if (xwork) GLS_TRY(mg.xwork.alloc(xwork));
   return mg_attach_common(c, p);
+}
+}  // namespace
+
+int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) { return mg_attach_nested(c, p, 0); }
+
+int gls_mg_attach_periodic(gls_ctx *c, const gls_mg_params *p, int periodic_mask) {
+  return mg_attach_nested(c, p, periodic_mask);
 }
 
 int gls_mg_attach_transfers(gls_ctx *c, const gls_mg_params *p, const int64_t *const *p_off, const int32_t *const *p_col,

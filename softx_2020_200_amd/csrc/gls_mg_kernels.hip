@@ -12,6 +12,8 @@
 // instantiation of gls_pencil_kernel, gls_brick_pencil.hip) and sums the bricks' coarse element vectors
 // with k_restrict_sum_cube (gls_brick_kernels.hip); gls_mg_attach checks these tap tables against that
 // kernel's closed form. The prolongation and every other hierarchy use the kernels below.
+// Periodic hyper_cubes (gls_mg_attach_periodic): a periodic axis has k n nodes, nf = 2 nc, and the two-pass kernels'
+// WRAP instantiations take their input modulo the lattice at the seam; the one-pass gather is not used there.
 // Multi-GPU: each rank works on the box sub-lattice its cells span (box gather / scatter through
 // a box -> local node map); nested partitions keep the coarse box the fine box's every-second node.
 #include "gls_launch.hpp"
@@ -72,9 +74,17 @@ __global__ void __launch_bounds__(256) k_transfer3d(const double *__restrict__ i
 // so the traffic is 1.6x the single-pass bytes with ~8x fewer loads than the 125-tap gather above.
 // A tile of OX x OY outputs reads the input x range [min first tap, max last tap] over its outputs,
 // <= IXM x IYM (checked on the host when the tables are built).
+// WRAP (lattices with a periodic axis, gls_mg_attach_periodic): the taps of a periodic axis are stored unwrapped
+// (below 0 or >= n at the seam, still ascending per output), so the window is the same contiguous range; the tile
+// takes its input node (x, y) modulo the lattice where it is loaded, the z pass its plane. The open-lattice
+// instantiation is compiled without any of it.
 #ifndef GLS_XFER_NT
 #define GLS_XFER_NT 1  // input tiles read non-temporally (neighbouring tiles share only their halo)
 #endif
+__device__ __forceinline__ int xfer_wrap(int i, int n) {  // i in (-n, 2 n) at every seam; any i is taken
+  i %= n;
+  return i < 0 ? i + n : i;
+}
 __device__ __forceinline__ double xfer_load(const double *p) {
 #if GLS_XFER_NT
   return __builtin_nontemporal_load(p);
@@ -82,7 +92,7 @@ __device__ __forceinline__ double xfer_load(const double *p) {
   return *p;
 #endif
 }
-template <int OX, int OY, int IXM, int IYM>
+template <int OX, int OY, int IXM, int IYM, bool WRAP>
 __global__ void __launch_bounds__(256) k_transfer_xy(const double *__restrict__ in, double *__restrict__ out, int i0,
                                                      int i1, int o0, int o1, int nz, int zb,
                                                      const int32_t *__restrict__ tx, const double *__restrict__ wx,
@@ -100,7 +110,7 @@ __global__ void __launch_bounds__(256) k_transfer_xy(const double *__restrict__ 
   const int nox = min(OX, o0 - ox0), noy = min(OY, o1 - oy0);
   const int tid = threadIdx.x;
   // input range of the tile: min first tap / max last tap over its outputs (each output's taps ascend)
-  if (tid < 4) s_rng[tid] = (tid & 1) ? -1 : 0x7fffffff;
+  if (tid < 4) s_rng[tid] = (tid & 1) ? (WRAP ? (int)0x80000000 : -1) : 0x7fffffff;
   __syncthreads();
   if (tid < nox) {
     atomicMin(&s_rng[0], tx[(ox0 + tid) * kMaxTaps]);
@@ -133,12 +143,18 @@ __global__ void __launch_bounds__(256) k_transfer_xy(const double *__restrict__ 
 #pragma unroll
   for (int u = 0; u < NV; ++u) {
     const int e = tid + u * 256, yy = e / (3 * nix), r = e - yy * 3 * nix;
-    offv[u] = e < niy * 3 * nix ? 3 * ((loy + yy) * i0 + lox) + r : -1;
+    if constexpr (WRAP)
+      offv[u] = e < niy * 3 * nix ? 3 * (xfer_wrap(loy + yy, i1) * i0 + xfer_wrap(lox + r / 3, i0)) + r % 3 : -1;
+    else
+      offv[u] = e < niy * 3 * nix ? 3 * ((loy + yy) * i0 + lox) + r : -1;
   }
 #pragma unroll
   for (int u = 0; u < NP; ++u) {
     const int e = tid + u * 256, yy = e / nix, xx = e - yy * nix;
-    offp[u] = e < niy * nix ? (loy + yy) * i0 + lox + xx : -1;
+    if constexpr (WRAP)
+      offp[u] = e < niy * nix ? xfer_wrap(loy + yy, i1) * i0 + xfer_wrap(lox + xx, i0) : -1;
+    else
+      offp[u] = e < niy * nix ? (loy + yy) * i0 + lox + xx : -1;
   }
   double rv[NV], rp[NP];
   auto load_plane = [&](int z) {
@@ -190,6 +206,7 @@ __global__ void __launch_bounds__(256) k_transfer_xy(const double *__restrict__ 
 }
 
 // z pass over whole planes of P nodes: out plane oz = sum_c wz[oz][c] in plane tz[oz][c]
+template <bool WRAP>
 __global__ void __launch_bounds__(256) k_transfer_z(const double *__restrict__ in, double *__restrict__ out, int64_t P,
                                                     int nzi, int nzo, const int32_t *__restrict__ tz,
                                                     const double *__restrict__ wz, const int32_t *__restrict__ cz) {
@@ -201,7 +218,11 @@ __global__ void __launch_bounds__(256) k_transfer_z(const double *__restrict__ i
     const int64_t pl = vel ? 3 * P : P;
     double v[kMaxTaps];
 #pragma unroll
-    for (int c = 0; c < kMaxTaps; ++c) v[c] = c < nc ? in[base_i + (int64_t)tz[oz * kMaxTaps + c] * pl] : 0.0;
+    for (int c = 0; c < kMaxTaps; ++c) {
+      int t = c < nc ? tz[oz * kMaxTaps + c] : 0;
+      if constexpr (WRAP) t = xfer_wrap(t, nzi);
+      v[c] = c < nc ? in[base_i + (int64_t)t * pl] : 0.0;
+    }
     double s = 0.0;
 #pragma unroll
     for (int c = 0; c < kMaxTaps; ++c) s += c < nc ? wz[oz * kMaxTaps + c] * v[c] : 0.0;
@@ -209,7 +230,7 @@ __global__ void __launch_bounds__(256) k_transfer_z(const double *__restrict__ i
   }
 }
 
-template <int OX, int OY, int IXM, int IYM>
+template <int OX, int OY, int IXM, int IYM, bool WRAP>
 hipError_t launch_transfer_xy(const double *in, double *out, int i0, int i1, int o0, int o1, int nz,
                               const int32_t *const taps[3], const double *const w[3], const int32_t *const cnt[3],
                               hipStream_t s, int add = 0) {
@@ -217,15 +238,16 @@ hipError_t launch_transfer_xy(const double *in, double *out, int i0, int i1, int
   // planes per block (prefetch pipeline depth): 2 planes (4x the blocks in flight of the former 8: 93.4-93.6 vs 93.8-94.1 ms per Newton step
   // at configs[2], profiles/r04_ab_transfer_planes.txt)
   const int zb = nz >= 16 ? 2 : 1;
-  hipLaunchKernelGGL((k_transfer_xy<OX, OY, IXM, IYM>), dim3(nb, (nz + zb - 1) / zb), dim3(256), 0, s, in, out, i0, i1,
+  hipLaunchKernelGGL((k_transfer_xy<OX, OY, IXM, IYM, WRAP>), dim3(nb, (nz + zb - 1) / zb), dim3(256), 0, s, in, out, i0, i1,
                      o0, o1, nz, zb, taps[0], w[0], cnt[0], taps[1], w[1], cnt[1], add);
   return hipGetLastError();
 }
 
+template <bool WRAP>
 hipError_t launch_transfer_z(const double *in, double *out, int64_t P, int nzi, int nzo, const int32_t *tz,
                              const double *wz, const int32_t *cz, hipStream_t s) {
   const int64_t b = (4 * P + 255) / 256;
-  hipLaunchKernelGGL(k_transfer_z, dim3((unsigned)std::min<int64_t>(b, 1024), nzo), dim3(256), 0, s, in, out, P, nzi,
+  hipLaunchKernelGGL(k_transfer_z<WRAP>, dim3((unsigned)std::min<int64_t>(b, 1024), nzo), dim3(256), 0, s, in, out, P, nzi,
                      nzo, tz, wz, cz);
   return hipGetLastError();
 }
@@ -418,19 +440,28 @@ int mg_transfer_tile_fits(int restrict_, int axis, int n_out, const int32_t *tap
   return 1;
 }
 
-hipError_t mg_transfer_2pass(const double *in, double *out, const int nin[3], const int nout[3], int restrict_,
-                             const int32_t *const taps[3], const double *const w[3], const int32_t *const cnt[3],
-                             double *work, hipStream_t s, int add) {
+template <bool WRAP>
+hipError_t transfer_2pass(const double *in, double *out, const int nin[3], const int nout[3], int restrict_,
+                          const int32_t *const taps[3], const double *const w[3], const int32_t *const cnt[3],
+                          double *work, hipStream_t s, int add) {
   if (restrict_) {  // xy (fine planes -> coarse xy), then z
-    const hipError_t e = launch_transfer_xy<kRestrictTile[0], kRestrictTile[1], kRestrictIn[0], kRestrictIn[1]>(
+    const hipError_t e = launch_transfer_xy<kRestrictTile[0], kRestrictTile[1], kRestrictIn[0], kRestrictIn[1], WRAP>(
         in, work, nin[0], nin[1], nout[0], nout[1], nin[2], taps, w, cnt, s);
     if (e != hipSuccess) return e;
-    return launch_transfer_z(work, out, (int64_t)nout[0] * nout[1], nin[2], nout[2], taps[2], w[2], cnt[2], s);
+    return launch_transfer_z<WRAP>(work, out, (int64_t)nout[0] * nout[1], nin[2], nout[2], taps[2], w[2], cnt[2], s);
   }
-  const hipError_t e = launch_transfer_z(in, work, (int64_t)nin[0] * nin[1], nin[2], nout[2], taps[2], w[2], cnt[2], s);
+  const hipError_t e =
+      launch_transfer_z<WRAP>(in, work, (int64_t)nin[0] * nin[1], nin[2], nout[2], taps[2], w[2], cnt[2], s);
   if (e != hipSuccess) return e;
-  return launch_transfer_xy<kProlongTile[0], kProlongTile[1], kProlongIn[0], kProlongIn[1]>(
+  return launch_transfer_xy<kProlongTile[0], kProlongTile[1], kProlongIn[0], kProlongIn[1], WRAP>(
       work, out, nin[0], nin[1], nout[0], nout[1], nout[2], taps, w, cnt, s, add);
+}
+
+hipError_t mg_transfer_2pass(const double *in, double *out, const int nin[3], const int nout[3], int restrict_,
+                             const int32_t *const taps[3], const double *const w[3], const int32_t *const cnt[3],
+                             double *work, hipStream_t s, int add, int wrap) {
+  return wrap ? transfer_2pass<true>(in, out, nin, nout, restrict_, taps, w, cnt, work, s, add)
+              : transfer_2pass<false>(in, out, nin, nout, restrict_, taps, w, cnt, work, s, add);
 }
 
 hipError_t mg_inject(const double *fine, double *coarse, const int nf[3], const int nc[3], hipStream_t s) {

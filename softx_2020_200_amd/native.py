@@ -31,7 +31,7 @@ EXPORTS = [
     "gls_mesh_hyper_cube", "gls_timing_reset", "gls_timing_get", "gls_timing_enable", "gls_uses_brick_kernels",
     "gls_part_create", "gls_part_sizes", "gls_part_get", "gls_part_destroy", "gls_dist_attach", "gls_dist_import", "gls_rccl_unique_id", "gls_rccl_create", "gls_rccl_destroy", "gls_rccl_info", "gls_mg_smoother_apply", "gls_mg_attach_replica",
     "gls_dist_attach_rccl",
-    "gls_mg_attach", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_ilu_plan", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
+    "gls_mg_attach", "gls_mg_attach_periodic", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_ilu_plan", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
     "gls_mg_residual_restrict", "gls_mg_prolong_smooth",
     "gls_prm_parse", "gls_prm_get", "gls_prm_n_entries", "gls_prm_entry", "gls_prm_destroy",
     "gls_expr_create", "gls_expr_n_components", "gls_expr_eval", "gls_expr_destroy", "gls_expr_eval_device",
@@ -189,6 +189,7 @@ def load():
     L.gls_timing_enable.argtypes = [vp, C.c_int]
     L.gls_uses_brick_kernels.argtypes = [vp]
     L.gls_mg_attach.argtypes = [vp, C.POINTER(MGParams)]
+    L.gls_mg_attach_periodic.argtypes = [vp, C.POINTER(MGParams), C.c_int]
     L.gls_mg_detach.argtypes = [vp]
     L.gls_mg_set_coarse_replica.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.gls_mg_attach_transfers.argtypes = [vp, C.POINTER(MGParams), C.POINTER(C.POINTER(i64)),
@@ -879,12 +880,15 @@ class GLSContext:
         check(self.L.gls_freeze_jacobian(self.h, 1 if freeze else 0), "gls_freeze_jacobian")
 
     def attach_multigrid(self, coarse_levels, pre_smooth=2, post_smooth=2, coarse_sweeps=30, omega=0.6,
-                         coarse_omega=0.0, coarse_direct=0, mixed_precision=0, level_sweeps=None, smoother_operator=0):
+                         coarse_omega=0.0, coarse_direct=0, mixed_precision=0, level_sweeps=None, smoother_operator=0,
+                         periodic=None):
         """GMRES right preconditioner = geometric multigrid V-cycle over [self] + coarse_levels
         (GLSContext objects of the same problem on hyper_cube(n/2^l)). Keeps references alive.
         level_sweeps: optional {level: (pre, post)} overriding pre_smooth / post_smooth per level
         (negative level indices count from the coarsest). smoother_operator=1: the FP32 smoothing J.v
-        applies the Oseen (Picard) linearization (gls_mg_params.smoother_operator)."""
+        applies the Oseen (Picard) linearization (gls_mg_params.smoother_operator). periodic: the periodic
+        directions of the levels' hyper_cubes, through gls_mg_attach_periodic (an empty tuple is its mask 0, which is
+        gls_mg_attach; None calls gls_mg_attach itself)."""
         levels = [self] + list(coarse_levels)
         arr = (C.c_void_p * len(levels))(*[lv.h for lv in levels])
         ls = None
@@ -897,8 +901,14 @@ class GLSContext:
             ls = (C.c_int * len(flat))(*flat)
         p = MGParams(len(levels), C.cast(arr, C.POINTER(C.c_void_p)), pre_smooth, post_smooth, coarse_sweeps, omega,
                      coarse_omega, coarse_direct, int(mixed_precision), ls, 0, int(smoother_operator))
-        check(self.L.gls_mg_attach(self.h, C.byref(p)), "gls_mg_attach")
+        if periodic is not None:
+            pm = sum(1 << d for d in set(periodic))
+            check(self.L.gls_mg_attach_periodic(self.h, C.byref(p), pm), "gls_mg_attach_periodic")
+        else:
+            check(self.L.gls_mg_attach(self.h, C.byref(p)), "gls_mg_attach")
         self._mg_levels = levels
+
+    mg_attach = attach_multigrid
 
     def attach_multigrid_transfers(self, coarse_levels, transfers, pre_smooth=2, post_smooth=2, coarse_sweeps=30,
                                    omega=0.6, coarse_omega=0.0, coarse_direct=0, level_sweeps=None, smoother="jacobi",

@@ -97,6 +97,53 @@ class CavityProblem:
             self.ctx.attach_multigrid([lv.ctx for lv in self.levels], **mg_opts)
 
 
+class PeriodicBoxProblem:
+    """3D hyper_cube(lo, hi) with the directions in `periodic` identified (the Taylor-Green box when all three are)
+    and no-slip walls on the faces of the other directions. The velocity nodes are the wrapped lexicographic lattice
+    (k n nodes on a periodic axis, k n + 1 elsewhere); `coords` holds their positions. multigrid=True: nested
+    periodic levels n/2, n/4, ... down to mg_coarsest cells per direction (4: a 2-cell periodic level is one brick
+    whose opposite faces are the same nodes), each with its own Dirichlet list, attached through
+    gls_mg_attach_periodic."""
+
+    def __init__(self, n=8, k=2, periodic=(0, 1, 2), lo=0.0, hi=2.0 * np.pi, viscosity=0.01, stream=None,
+                 multigrid=False, mg_coarsest=4, **mg_opts):
+        self.dim, self.n, self.k, self.kp, self.periodic = 3, n, k, k, tuple(sorted(set(periodic)))
+        self.mesh = hyper_cube(3, n, k, k, lo, hi, periodic=self.periodic)
+        self.shape = [k * n if d in self.periodic else k * n + 1 for d in range(3)]
+        idx = np.indices(self.shape[::-1]).reshape(3, -1)[::-1].T  # lexicographic, x fastest
+        self.coords = lo + idx * ((hi - lo) / (k * n))
+        wall = np.zeros(idx.shape[0], dtype=bool)
+        for d in range(3):
+            if d not in self.periodic:
+                wall |= (idx[:, d] == 0) | (idx[:, d] == self.shape[d] - 1)
+        self.vnode_mask = np.where(wall, 7, 0).astype(np.uint8)
+        nodes = np.nonzero(wall)[0]
+        self.dir_dofs = (nodes[:, None] * 3 + np.arange(3)[None]).reshape(-1).astype(np.int64)
+        self.dir_vals = np.zeros(self.dir_dofs.size)
+        self.ctx = build_context(self.mesh, viscosity=viscosity, vnode_mask=self.vnode_mask, stream=stream)
+        if self.dir_dofs.size:
+            self.ctx.set_dirichlet(self.dir_dofs, self.dir_vals)
+        self.n_dofs = self.ctx.n_dofs
+        self.levels = []
+        if multigrid:
+            m = n
+            while m % 2 == 0 and m // 2 >= mg_coarsest:
+                m //= 2
+                self.levels.append(PeriodicBoxProblem(m, k, self.periodic, lo, hi, viscosity, stream))
+            self.ctx.attach_multigrid([lv.ctx for lv in self.levels], periodic=self.periodic, **mg_opts)
+
+    def taylor_green(self, t=0.0):
+        """the Taylor-Green vortex at the nodes (the initial condition of apps/cases/tgv3d_*.prm) with amplitude
+        1 - t, the walls' values put in: a smooth state and, for t > 0, smooth histories"""
+        x, y, z = self.coords.T
+        a = 1.0 - t
+        vel = np.stack([a * np.cos(x) * np.sin(y) * np.cos(z), -a * np.sin(x) * np.cos(y) * np.cos(z), 0 * x], 1)
+        p = -a * a / 16.0 * (np.cos(2 * x) + np.cos(2 * y)) * (np.cos(2 * z) + 2.0)
+        u = np.concatenate([vel.reshape(-1), p])
+        u[self.dir_dofs] = self.dir_vals
+        return u
+
+
 def octree_lid_tree(n=4, steps=3, dim=3, base=2):
     """An adapted forest for the cavity: n^dim cells (a base^dim forest refined globally to n per
     direction, so the multigrid hierarchy reaches down to base^dim cells), then `steps` refinements of
