@@ -162,6 +162,11 @@ struct Params {
   int refinement = 0;
   // general meshes (gls_umesh): mesh type gmsh or a non-hyper_cube deal.II grid
   bool general = false;
+  // --box-path brick on a (subdivided_)hyper_rectangle: the brick path on gls_mesh_hyper_rectangle's mesh instead of
+  // the general one; box_cells = subdivisions * 2^refinement per axis, corners box_p1 / box_p2 (apply_box_path)
+  bool box = false;
+  int box_cells[3] = {0, 0, 0};
+  double box_p1[3] = {0, 0, 0}, box_p2[3] = {0, 0, 0};
   std::string mesh_type = "dealii", grid_type = "hyper_cube", grid_args = "-1 : 1 : false", mesh_file;
   bool qmapping_all = false;
   struct ManifoldPrm { int id = 0; std::string type = "none"; double arg[3] = {0, 0, 0}; };
@@ -411,12 +416,76 @@ Params read_params(const Prm &p, int dim) {
   return P;
 }
 
+// --box-path brick: the conditions under which a (subdivided_)hyper_rectangle runs on the brick path (3D, k == kp <= 2,
+// one rank, no Kelly adaptation, an even cell count subdivisions * 2^refinement on every axis). Empty: P is switched
+// to the box path (general = false, the box's counts and corners); else the condition that failed, P untouched.
+// Before any GPU call.
+std::string apply_box_path(Params &P, int np_ranks) {
+  if (P.mesh_type != "dealii" || (P.grid_type != "hyper_rectangle" && P.grid_type != "subdivided_hyper_rectangle"))
+    return "grid type '" + P.grid_type + "' is not hyper_rectangle or subdivided_hyper_rectangle";
+  if (P.dim != 3) return "the box path is 3D only";
+  if (P.k != P.kp || P.k > 2) return "the box path needs equal orders k == kp <= 2";
+  if (np_ranks != 1) return "the box path runs on one rank";
+  // the condition under which run() calls refine_kelly(): the type alone (a transient run adapts every `frequency`
+  // steps whatever `number mesh adapt` is)
+  if (P.madapt == "kelly") return "Kelly mesh adaptation is not available on the box path";
+  if (!P.manifolds.empty()) return "manifolds are not available on the box path";
+  std::vector<std::string> parts;
+  {
+    std::stringstream ss(P.grid_args);
+    std::string tok;
+    while (std::getline(ss, tok, ':')) parts.push_back(trim(tok));
+  }
+  const bool sub = P.grid_type == "subdivided_hyper_rectangle";
+  const size_t o = sub ? 1 : 0;
+  if (parts.size() < o + 2) return "grid arguments '" + P.grid_args + "' are not '" + (sub ? "nx, ny, nz : " : "") + "p1 : p2 : colorize'";
+  auto triple = [](const std::string &t, double out[3]) {
+    std::stringstream ss(t);
+    std::string tok;
+    int n = 0;
+    while (n < 3 && std::getline(ss, tok, ',')) out[n++] = std::atof(trim(tok).c_str());
+    return n == 3;
+  };
+  double rep[3] = {1, 1, 1}, p1[3], p2[3];
+  if ((sub && !triple(parts[0], rep)) || !triple(parts[o], p1) || !triple(parts[o + 1], p2))
+    return "grid arguments '" + P.grid_args + "' do not hold three values per point";
+  if (P.refinement < 0 || P.refinement > 20) return "initial refinement out of range";
+  int cells[3];
+  for (int d = 0; d < 3; ++d) {
+    if (rep[d] < 1 || rep[d] != std::floor(rep[d]) || rep[d] > 4096) return "subdivisions must be integers >= 1";
+    const int64_t c = (int64_t)rep[d] << P.refinement;
+    if (c % 2 != 0 || c > (1 << 20)) {
+      char b[160];
+      std::snprintf(b, sizeof b, c % 2 != 0 ? "subdivisions * 2^refinement = %lld on axis %d is not even"
+                                            : "subdivisions * 2^refinement = %lld on axis %d is more than 2^20 cells",
+                    (long long)c, d);
+      return b;
+    }
+    if (!(p2[d] > p1[d])) return "the box needs p1 < p2 on every axis";
+    cells[d] = (int)c;
+  }
+  P.general = false;
+  P.box = true;
+  P.colorize = parts.size() > o + 2 && parts[o + 2] == "true";
+  for (int d = 0; d < 3; ++d) {
+    P.box_cells[d] = cells[d];
+    P.box_p1[d] = p1[d];
+    P.box_p2[d] = p2[d];
+  }
+  P.lo = p1[0];  // (the cube's scalars are not read on the box path)
+  P.hi = p2[0];
+  return "";
+}
+
 // ---------------------------------------------------------------------------------------------
 // mesh and constraints
 // ---------------------------------------------------------------------------------------------
 struct Mesh {
-  int dim = 3, n = 1, k = 1, kp = 1, pmask = 0;
-  double lo = 0, hi = 1, hc = 1;
+  int dim = 3, k = 1, kp = 1, pmask = 0;
+  // the box per axis: cells, corners and cell size (hyper_cube: the three-equal case)
+  int n[3] = {1, 1, 1};
+  double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1}, hc[3] = {1, 1, 1};
+  bool box = false;  // --box-path brick: the subdivided hyper_rectangle of gls_mesh_hyper_rectangle
   int64_t nc = 0, nv = 0, np = 0;
   int vsh[3] = {1, 1, 1}, psh[3] = {1, 1, 1};  // lattice nodes per direction (periodic: wrapped)
   std::vector<int32_t> cv, cp;
@@ -453,7 +522,7 @@ struct Mesh {
     for (int d = 0; d < dim; ++d) {
       idx[d] = (int)(node % sh[d]);
       node /= sh[d];
-      x[d] = lo + idx[d] * hc / deg;
+      x[d] = lo[d] + idx[d] * hc[d] / deg;
     }
   }
 };
@@ -461,13 +530,15 @@ struct Mesh {
 Mesh build_mesh(const Params &P, int n, int pmask) {
   Mesh m;
   m.dim = P.dim;
-  m.n = n;
   m.k = P.k;
   m.kp = P.kp;
   m.pmask = pmask;
-  m.lo = P.lo;
-  m.hi = P.hi;
-  m.hc = (P.hi - P.lo) / n;
+  for (int d = 0; d < 3; ++d) {
+    m.n[d] = n;
+    m.lo[d] = P.lo;
+    m.hi[d] = P.hi;
+    m.hc[d] = (P.hi - P.lo) / n;
+  }
   ck(gls_mesh_hyper_cube_sizes(P.dim, n, P.k, P.kp, pmask, &m.nc, &m.nv, &m.np), "gls_mesh_hyper_cube_sizes");
   int nvl = 1, npl = 1;
   for (int d = 0; d < P.dim; ++d) {
@@ -496,10 +567,47 @@ Mesh build_mesh(const Params &P, int n, int pmask) {
   return m;
 }
 
+// the subdivided hyper_rectangle of --box-path brick: cells[a] cells per axis (gls_mesh_hyper_rectangle)
+Mesh build_box_mesh(const Params &P, const int cells[3], int pmask) {
+  Mesh m;
+  m.dim = 3;
+  m.k = P.k;
+  m.kp = P.kp;
+  m.pmask = pmask;
+  m.box = true;
+  for (int d = 0; d < 3; ++d) {
+    const bool per = (pmask >> d) & 1;
+    m.n[d] = cells[d];
+    m.lo[d] = P.box_p1[d];
+    m.hi[d] = P.box_p2[d];
+    m.hc[d] = (P.box_p2[d] - P.box_p1[d]) / cells[d];
+    m.vsh[d] = P.k * cells[d] + (per ? 0 : 1);
+    m.psh[d] = P.kp * cells[d] + (per ? 0 : 1);
+  }
+  ck(gls_mesh_hyper_rectangle_sizes(3, cells, P.k, P.kp, pmask, &m.nc, &m.nv, &m.np), "gls_mesh_hyper_rectangle_sizes");
+  const int nvl = (P.k + 1) * (P.k + 1) * (P.k + 1), npl = (P.kp + 1) * (P.kp + 1) * (P.kp + 1);
+  m.cv.resize((size_t)(m.nc * nvl));
+  m.cp.resize((size_t)(m.nc * npl));
+  m.x0.resize((size_t)(m.nc * 3));
+  m.h.resize((size_t)(m.nc * 3));
+  ck(gls_mesh_hyper_rectangle(3, cells, P.k, P.kp, P.box_p1, P.box_p2, pmask, m.cv.data(), m.cp.data(), m.x0.data(),
+                              m.h.data()),
+     "gls_mesh_hyper_rectangle");
+  if (pmask) {  // deal.II's count: the unwrapped lattices
+    int64_t nvf = 1, npf = 1;
+    for (int d = 0; d < 3; ++d) {
+      nvf *= (int64_t)P.k * cells[d] + 1;
+      npf *= (int64_t)P.kp * cells[d] + 1;
+    }
+    m.n_dofs_dealii = 3 * nvf + npf;
+  }
+  return m;
+}
+
 // the support point x lies on the box face lo (side 0) / hi (side 1) of axis d
 bool on_face(const Mesh &m, const double *x, int d, int side) {
-  const double tol = 1e-12 * (m.hi - m.lo);
-  return std::fabs(x[d] - (side ? m.hi : m.lo)) <= tol;
+  const double tol = 1e-12 * (m.hi[d] - m.lo[d]);
+  return std::fabs(x[d] - (side ? m.hi[d] : m.lo[d])) <= tol;
 }
 // boundary ids of a support point (hyper_cube: colorize -> faces 2d / 2d+1, else all id 0)
 unsigned face_bits(const Mesh &m, const double *x, bool colorize) {
@@ -1481,12 +1589,14 @@ struct Solver {
     const int npl = dim == 3 ? (P.kp + 1) * (P.kp + 1) * (P.kp + 1) : (P.kp + 1) * (P.kp + 1);
     Mesh r;
     r.dim = dim;
-    r.n = 1;
     r.k = P.k;
     r.kp = P.kp;
-    r.lo = P.lo;
-    r.hi = P.hi;
-    r.hc = P.hi - P.lo;
+    for (int d = 0; d < 3; ++d) {
+      r.n[d] = 1;
+      r.lo[d] = P.lo;
+      r.hi[d] = P.hi;
+      r.hc[d] = P.hi - P.lo;
+    }
     r.nc = R.n_cells;
     r.nv = R.n_vnodes;
     r.np = R.n_pnodes;
@@ -1647,6 +1757,70 @@ struct Solver {
     }
     (void)N;
     print_setup(std::pow(P.hi - P.lo, P.dim));
+    build_boundary_plan();
+  }
+
+  // --box-path brick: the subdivided hyper_rectangle on the brick path. The nested multigrid (gls_mg_attach_box) where
+  // at least two levels exist -- every level's counts even, >= 2 on an open and >= 4 on a periodic axis -- and the
+  // coarsest fits the dense direct solve (40000 DoFs); the steady, fully periodic case keeps the ILU as on the cube.
+  bool mg_box = false;
+  int mg_box_coarsest[3] = {0, 0, 0};
+  void setup_box(const int cells[3]) {
+    SectionTimer::Scope ts(timer, "setup_dofs");
+    release();
+    m = build_box_mesh(P, cells, periodic_mask());
+    C = make_constraints(P, m, time);
+    ctx = make_context(m, C);
+    alloc_vectors();
+    mg_periodic = false;
+    mg_box = false;
+    mg_steady_periodic = use_mg && forest_mode != 1 && m.pmask == 7 && P.method == Method::steady;
+    const bool mg_mask_ok = m.pmask == 0 || (!mg_steady_periodic && forest_mode != 1);
+    if (use_mg && mg_mask_ok) {
+      std::vector<std::array<int, 3>> lc;
+      std::array<int, 3> c{cells[0], cells[1], cells[2]};
+      for (;;) {
+        bool ok = true;
+        for (int d = 0; d < 3; ++d) ok = ok && c[d] % 4 == 0 && c[d] / 2 >= (((m.pmask >> d) & 1) ? 4 : 2);
+        if (!ok) break;
+        for (int d = 0; d < 3; ++d) c[d] /= 2;
+        lc.push_back(c);
+      }
+      int64_t nco = 0;
+      if (!lc.empty()) {
+        int64_t nv = 1;
+        for (int d = 0; d < 3; ++d) nv *= (int64_t)P.k * lc.back()[d] + (((m.pmask >> d) & 1) ? 0 : 1);
+        nco = 4 * nv;
+      }
+      if (!lc.empty() && nco <= 40000) {
+        std::vector<gls_ctx *> lv{ctx};
+        for (const auto &cl : lc) {
+          const Mesh mc = build_box_mesh(P, cl.data(), m.pmask);
+          const Constraints cc = make_constraints(P, mc, time);
+          gls_ctx *g = make_context(mc, cc);
+          mg_levels.push_back(g);
+          lv.push_back(g);
+        }
+        gls_mg_params mp;
+        std::memset(&mp, 0, sizeof(mp));
+        mp.n_levels = (int)lv.size();
+        mp.levels = lv.data();
+        mp.pre_smooth = 1;
+        mp.post_smooth = 1;
+        mp.omega = m.pmask ? 0.6 : 0.9;  // the cube's dampings (setup)
+        mp.coarse_omega = mp.omega;
+        mp.coarse_direct = 1;  // pressure pinned: exact whether or not a velocity is fixed
+        mp.mixed_precision = 1;
+        mp.smoother_operator = 1;
+        ck(gls_mg_attach_box(ctx, &mp, cells, m.pmask), "gls_mg_attach_box");
+        mg_box = true;
+        for (int d = 0; d < 3; ++d) mg_box_coarsest[d] = lc.back()[d];
+      }
+    }
+    if (rank == 0)
+      std::fprintf(stderr, "box path: brick (gls_mesh_hyper_rectangle, %d x %d x %d cells; multigrid %s)\n", cells[0], cells[1],
+                   cells[2], mg_box ? "attached" : "not attached");
+    print_setup((P.box_p2[0] - P.box_p1[0]) * (P.box_p2[1] - P.box_p1[1]) * (P.box_p2[2] - P.box_p1[2]));
     build_boundary_plan();
   }
 
@@ -2273,6 +2447,10 @@ struct Solver {
                     mg_smoother_used == 3 ? "additive cell-Vanka" : mg_smoother_used ? "ILU(0)" : "damped-Jacobi",
                     rmesh ? "forest's" : "triangulation's", mg_levels.size() + 1,
                     coarse_words.c_str());
+    else if (!mg_levels.empty() && mg_box)
+      std::snprintf(prec, sizeof prec, "geometric multigrid V(1,1)-cycle on the nested hyper_rectangles (%zu levels, coarsest "
+                                       "%d x %d x %d cells, unfused transfers)",
+                    mg_levels.size() + 1, mg_box_coarsest[0], mg_box_coarsest[1], mg_box_coarsest[2]);
     else if (!mg_levels.empty() && mg_periodic)
       std::snprintf(prec, sizeof prec, "periodic geometric multigrid V(1,1)-cycle on the nested periodic hyper_cubes "
                                        "(%zu levels, coarsest 4 cells per direction, unfused wrap-aware transfers)",
@@ -2707,7 +2885,12 @@ struct Solver {
     }
     const Mesh old = m;
     const std::vector<double> sol = present;
-    setup(m.n * 2);
+    if (old.box) {
+      const int c2[3] = {2 * old.n[0], 2 * old.n[1], 2 * old.n[2]};
+      setup_box(c2);
+    } else {
+      setup(m.n[0] * 2);
+    }
     const int dim = old.dim;
     auto value_at = [&](const double *x, int comp) {
       const bool vel = comp < dim;
@@ -2716,8 +2899,8 @@ struct Solver {
       int ci[3] = {0, 0, 0};
       double b[3][4], db[4];
       for (int d = 0; d < dim; ++d) {
-        const double s = (x[d] - old.lo) / old.hc;
-        ci[d] = std::min((int)std::floor(s), old.n - 1);
+        const double s = (x[d] - old.lo[d]) / old.hc[d];
+        ci[d] = std::min((int)std::floor(s), old.n[d] - 1);
         lag1d(xn, s - ci[d], b[d], db);
       }
       const int nl = dim == 3 ? kk * kk * kk : kk * kk;
@@ -2759,6 +2942,8 @@ struct Solver {
   // `initial refinement` times, so leaf levels are deal.II's cell levels.
   void refine_kelly() {
     SectionTimer::Scope ts(timer, "refine");
+    // the forest below is the hyper_cube's one coarse cell; apply_box_path never lets a Kelly prm onto the box path
+    if (m.box) die("kelly mesh adaptation is not available on the box path (--box-path brick)");
     if (m.general) {
       refine_kelly_general();
       return;
@@ -3047,13 +3232,13 @@ struct Solver {
       // else 0); periodic directions have no boundary
       std::vector<double> gx, gw;
       gauss01(nq, gx, gw);
-      const double tol = 1e-12 * (m.hi - m.lo);
       for (int64_t c = 0; c < m.nc; ++c)
         for (int d = 0; d < dim; ++d)
           for (int s = 0; s < 2; ++s) {
             if ((m.pmask >> d) & 1) continue;
+            const double tol = 1e-12 * (m.hi[d] - m.lo[d]);
             const double *x0 = &m.x0[(size_t)(c * dim)], *h = &m.h[(size_t)(c * dim)];
-            if (std::fabs(x0[d] + s * h[d] - (s ? m.hi : m.lo)) > tol) continue;
+            if (std::fabs(x0[d] + s * h[d] - (s ? m.hi[d] : m.lo[d])) > tol) continue;
             int t[2] = {0, 0}, nt = 0;
             for (int e = 0; e < dim; ++e)
               if (e != d) t[nt++] = e;
@@ -3231,7 +3416,9 @@ struct Solver {
     dts[0] = P.dt;
     std::printf("Running on %d MPI rank(s)...\n", world);  // navier_stokes_base.cc:115-117 (one rank per GPU)
     if (world > 1 && !P.general) P.general = true;  // --np: every mesh through the general (partitioned) path
-    if (P.general) {
+    if (P.box) {
+      setup_box(P.box_cells);
+    } else if (P.general) {
       create_umesh();
       setup_general();
     } else {
@@ -3341,7 +3528,10 @@ int main(int argc, char **argv) {
   // final state for the pipeline tests), --output-eval host|device (the VTU point data from the host vector or,
   // the default, on the device from the device-resident solution), --error-eval host|device (the L2 error against
   // the analytical solution from the host vector, the default, or on the device), --ic-eval host|device (the
-  // L2projection initial condition by the host conjugate gradients, the default, or on the device).
+  // L2projection initial condition by the host conjugate gradients, the default, or on the device),
+  // --box-path brick|general (a hyper_rectangle / subdivided_hyper_rectangle on the brick kernels and the nested
+  // multigrid where 3D, k == kp <= 2, one rank, no Kelly adaptation and even cell counts allow it; general, the
+  // default: the general-mesh path; a condition that fails is named on stderr and the general path taken).
   int dim = 0;
   bool output_device = true, error_device = false, ic_device = false;
   bool mg = true, stats = false;
@@ -3352,6 +3542,7 @@ int main(int argc, char **argv) {
   int forest_mode = 0;
   int mg_smoother = -1, mg_sweeps = 0;
   int coarse_storage = 0;
+  bool box_brick = false;
   int precision = 4;
   const char *file = nullptr;
   const std::string prog = argv[0];
@@ -3387,6 +3578,11 @@ int main(int argc, char **argv) {
       else die("--coarse-storage %s: auto, dense or band", v);
     }
     else if (!std::strcmp(argv[i], "--ilu-block-dofs") && i + 1 < argc) ilu_block = std::atoll(argv[++i]);
+    else if (!std::strcmp(argv[i], "--box-path") && i + 1 < argc) {
+      const char *o = argv[++i];
+      if (std::strcmp(o, "brick") && std::strcmp(o, "general")) die("--box-path %s: brick or general", o);
+      box_brick = !std::strcmp(o, "brick");
+    }
     else if (!std::strcmp(argv[i], "--dump") && i + 1 < argc) dump = argv[++i];
     else if (!std::strcmp(argv[i], "--np") && i + 1 < argc) np_ranks = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--ilu-order") && i + 1 < argc) {
@@ -3425,6 +3621,10 @@ int main(int argc, char **argv) {
   // --np N: N ranks forked here, before any GPU call (the children's stdout is discarded: rank 0
   // prints, as the reference's pcout does)
   if (np_ranks < 1 || np_ranks > kMaxRanks) die("--np must be in 1..%d", kMaxRanks);
+  if (box_brick) {  // opt-in: a (subdivided_)hyper_rectangle on the brick path where its conditions hold
+    const std::string why = apply_box_path(P, np_ranks);
+    if (!why.empty()) std::fprintf(stderr, "box path: general (--box-path brick not taken: %s)\n", why.c_str());
+  }
   if (coarse_storage == 2 && np_ranks > 1) die("--coarse-storage band runs on one rank (--np 1)");
   int rank = 0;
   std::vector<pid_t> kids;

@@ -91,6 +91,11 @@ int gls_quadrature_points(const gls_ctx *ctx, double *xq);
 /* 1 when the context runs the sum-factorized brick kernels (3D Qk-Qk on Morton 2x2x2 bricks),
  * 0 for the general per-cell kernels. GLS_DISABLE_BRICK=1 in the environment forces 0. */
 int gls_uses_brick_kernels(const gls_ctx *ctx);
+/* How the context sums the bricks' surface slab: 0 through the node -> slot index map (or not at all: no brick
+ * kernels), 1 by the closed form of the verified hyper_cube (Morton bricks), 2 by the closed form of the verified open
+ * subdivided hyper_rectangle (tile-Morton bricks, gls_mesh_hyper_rectangle). nb[3] (bricks per axis) and tile (bricks
+ * per tile edge; the cube: its brick count) are set for 1 and 2; either may be NULL. */
+int gls_slab_lattice(const gls_ctx *ctx, int nb[3], int *tile);
 /* Rewrite the forcing at quadrature points (host pointer, [n_cells*nq*dim]) or clear it (NULL). */
 int gls_set_force(gls_ctx *ctx, const double *force_q);
 int gls_set_viscosity(gls_ctx *ctx, double viscosity);
@@ -280,6 +285,17 @@ int gls_mg_attach(gls_ctx *ctx, const gls_mg_params *prm);
  * it had): a level that is not that lattice (the level is named), a distributed context or level with a non-zero
  * mask, a level with fewer than 2 cells per direction, and whatever gls_mg_attach refuses. One GPU. */
 int gls_mg_attach_periodic(gls_ctx *ctx, const gls_mg_params *prm, int periodic_mask);
+/* The same hierarchy on subdivided hyper_rectangles (gls_mesh_hyper_rectangle): level l has cells[a] >> l cells on
+ * axis a, every count even on every level (the coarsest included: the levels are brick meshes), at least 2 cells on
+ * an open axis and 4 on a periodic one. Every level, mask 0 included, is checked cell by cell against the wrapped
+ * lexicographic lattice of its counts (any cell order); nf = 2 nc - 1 across an open axis and 2 nc across a periodic
+ * one, tap tables and two-pass transfers as in gls_mg_attach_periodic. The transfers fused into the smoother launches
+ * stay the open cube's: cells = (n, n, n) with mask 0 is gls_mg_attach, with a mask gls_mg_attach_periodic (the same
+ * transfers and V-cycle, bitwise); every other box reports fused = 0. GLS_EINVAL with a message naming the level and
+ * the axis, before anything is detached (the context keeps the hierarchy it had): an odd count, too few cells, a
+ * level whose cell count or numbering is not that lattice, a distributed context or level, and whatever
+ * gls_mg_attach refuses. One GPU. */
+int gls_mg_attach_box(gls_ctx *ctx, const gls_mg_params *prm, const int cells[3], int periodic_mask);
 /* The same V-cycle on a general level hierarchy with the caller's grid transfers: levels of an adaptive
  * (octree) mesh with hanging-node constraints (gls_set_hanging before attaching), e.g. the global
  * coarsening gls_octree_coarsen_to / gls_octree_mg_transfer builds. For l = 0 .. n_levels-2:
@@ -677,6 +693,24 @@ int gls_mesh_hyper_cube_sizes(int dim, int n, int k, int kp, int periodic_mask,
                               int64_t *n_cells, int64_t *n_vnodes, int64_t *n_pnodes);
 int gls_mesh_hyper_cube(int dim, int n, int k, int kp, double lo, double hi, int periodic_mask,
                         int32_t *cell_vnodes, int32_t *cell_pnodes, double *cell_x0, double *cell_h);
+
+/* subdivided_hyper_rectangle mesh (GridGenerator::subdivided_hyper_rectangle + refine_global): cells[a] cells on axis
+ * a of the box p1 .. p2, each count even and >= 2; dim = 3 only (GLS_EINVAL otherwise). The same arrays as
+ * gls_mesh_hyper_cube, cell_h[c] = (p2 - p1) / cells per axis. Nodes: the lexicographic lattice, x fastest, with
+ * K cells[a] + 1 nodes on axis a, K cells[a] where bit a of periodic_mask is set (the high face is the low face).
+ * Cells: bricks of 2 x 2 x 2 cells, a brick's 8 cells in the order cx + 2 cy + 4 cz, the bricks in "tile-Morton"
+ * order: nb[a] = cells[a] / 2 bricks per axis, s = the largest power of two dividing all three nb[a]; tiles of s^3
+ * bricks run lexicographically, tx fastest, and the bricks of a tile in Morton order of (bx % s, by % s, bz % s):
+ *   brick(bx, by, bz) = ((tz nty + ty) ntx + tx) s^3 + morton3(bx % s, by % s, bz % s),  t = b / s, nt = nb / s.
+ * cells = (n, n, n) with n a power of two is the Morton order: the arrays equal gls_mesh_hyper_cube's bit for bit.
+ * A context created on the open mesh (mask 0, nb[a] <= 2048) recognises the lattice and sums the brick-surface slab
+ * by this closed form instead of the index map (GLS_SLAB_CSR=1 at gls_create: the map). boundary ids: the cube's,
+ * colorize ? 2d / 2d+1 : 0. */
+int gls_mesh_hyper_rectangle_sizes(int dim, const int cells[3], int k, int kp, int periodic_mask,
+                                   int64_t *n_cells, int64_t *n_vnodes, int64_t *n_pnodes);
+int gls_mesh_hyper_rectangle(int dim, const int cells[3], int k, int kp, const double p1[3], const double p2[3],
+                             int periodic_mask, int32_t *cell_vnodes, int32_t *cell_pnodes, double *cell_x0,
+                             double *cell_h);
 
 /* Locally refined hyper_cube (one extra level): hyper_cube(lo, hi) with n^dim cells, the cells
  * flagged in refine[n^dim] (lexicographic, x fastest; NULL = none) split into 2^dim children

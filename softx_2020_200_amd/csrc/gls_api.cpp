@@ -20,6 +20,7 @@
 #include <vector>
 #include <set>
 
+#include "gls_box_mesh.hpp"
 #include "gls_ctx.hpp"
 #include "gls_incidence.hpp"
 
@@ -346,6 +347,17 @@ int build_slab_map(gls_ctx *c, const gls_mesh_desc *d) {
     }
     if (ok) c->cube_nb1 = (int)(n / 2);
   }
+  // open subdivided hyper_rectangle (gls_mesh_hyper_rectangle, mask 0: lexicographic node lattice, bricks in
+  // tile-Morton order), verified cell by cell like the cube; consulted only where cube_nb1 == 0
+  c->box_nb[0] = c->box_nb[1] = c->box_nb[2] = 0;
+  c->box_s = 0;
+  if (!std::getenv("GLS_SLAB_CSR")) {
+    int nbb[3], s = 0;
+    if (gls_impl::box_lattice_detect(d->n_cells, d->n_vnodes, K, d->cell_vnodes, nbb, &s)) {
+      for (int a = 0; a < 3; ++a) c->box_nb[a] = nbb[a];
+      c->box_s = s;
+    }
+  }
   // brick coloring: greedy in brick (Morton) order over the bricks sharing a surface node
   if (!gls::brick_colors_supported(K)) return GLS_OK;  // only in a -DGLS_BRICK_COLORS_BUILD library (A/B)
   std::vector<int> color((size_t)nb, -1);
@@ -666,6 +678,9 @@ hipError_t slab_sum_ex(gls_ctx *g, const double *slab, const float *slabf, doubl
   if (g->cube_nb1 > 0)
     return gls::brick_slab_sum_cube(g->k, g->cube_nb1, slab, slabf, g->n_vnodes, y, vmask, jb, jd, omega, g->stream, rb,
                                     x0, xs);
+  if (g->box_nb[0] > 0 && !xs)
+    return gls::brick_slab_sum_box(g->k, g->box_nb, g->box_s, slab, slabf, g->n_vnodes, y, vmask, jb, jd, omega, g->stream,
+                                   rb, x0);
   if (x0 || xs) return hipErrorInvalidValue;
   return gls::brick_slab_sum_ex(slab, slabf, g->sum_nodes.p, g->sum_off.p, g->sum_slots.p, (int64_t)g->sum_nodes.n,
                                 g->n_vnodes, y, vmask, jb, jd, omega, g->stream, rb);
@@ -674,6 +689,9 @@ hipError_t slab_sum(gls_ctx *c, double *y) {
   if (c->cube_nb1 > 0)
     return gls::brick_slab_sum_cube(c->k, c->cube_nb1, c->slab.p, nullptr, c->n_vnodes, y, nullptr, nullptr, nullptr, 0.0,
                                     c->stream);
+  if (c->box_nb[0] > 0)
+    return gls::brick_slab_sum_box(c->k, c->box_nb, c->box_s, c->slab.p, nullptr, c->n_vnodes, y, nullptr, nullptr, nullptr,
+                                   0.0, c->stream);
   return gls::brick_slab_sum(c->slab.p, c->sum_nodes.p, c->sum_off.p, c->sum_slots.p, (int64_t)c->sum_nodes.n,
                              c->n_vnodes, y, c->stream);
 }
@@ -1139,6 +1157,15 @@ int gls_set_stream(gls_ctx *c, void *s) {
 }
 
 int gls_uses_brick_kernels(const gls_ctx *c) { return c && c->use_brick ? 1 : 0; }
+
+int gls_slab_lattice(const gls_ctx *c, int nb[3], int *tile) {
+  if (!c || !c->use_brick || !c->use_slab) return 0;
+  const bool cube = c->cube_nb1 > 0;
+  if (!cube && c->box_nb[0] <= 0) return 0;
+  for (int a = 0; a < 3 && nb; ++a) nb[a] = cube ? c->cube_nb1 : c->box_nb[a];
+  if (tile) *tile = cube ? c->cube_nb1 : c->box_s;
+  return cube ? 1 : 2;
+}
 
 int gls_quadrature_points(const gls_ctx *c, double *xq) {
   if (!c || !xq) return set_err(GLS_EINVAL, "null argument");
@@ -2631,6 +2658,24 @@ int gls_mesh_hyper_cube(int dim, int n, int k, int kp, double lo, double hi, int
     ++cell;
   }
   return cell == nc ? GLS_OK : set_err(GLS_EINVAL, "morton enumeration mismatch");
+}
+
+// --------------------------------------------------------------------------------------------
+// subdivided_hyper_rectangle + refine_global: bricks in tile-Morton order (gls_box_mesh.hpp), lexicographic nodes
+// --------------------------------------------------------------------------------------------
+int gls_mesh_hyper_rectangle_sizes(int dim, const int cells[3], int k, int kp, int pmask, int64_t *nc, int64_t *nv,
+                                   int64_t *np) {
+  if (dim != 3) return set_err(GLS_EINVAL, "gls_mesh_hyper_rectangle: 3D only (dim %d)", dim);
+  if (const char *why = gls_impl::box_mesh_sizes(cells, k, kp, pmask, nc, nv, np)) return set_err(GLS_EINVAL, "%s", why);
+  return GLS_OK;
+}
+
+int gls_mesh_hyper_rectangle(int dim, const int cells[3], int k, int kp, const double p1[3], const double p2[3], int pmask,
+                             int32_t *cv, int32_t *cp, double *x0, double *h) {
+  if (dim != 3) return set_err(GLS_EINVAL, "gls_mesh_hyper_rectangle: 3D only (dim %d)", dim);
+  if (const char *why = gls_impl::box_mesh_fill(cells, k, kp, p1, p2, pmask, cv, cp, x0, h))
+    return set_err(GLS_EINVAL, "%s", why);
+  return GLS_OK;
 }
 
 // --------------------------------------------------------------------------------------------

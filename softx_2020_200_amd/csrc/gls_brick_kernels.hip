@@ -1381,6 +1381,172 @@ hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *
   return hipGetLastError();
 }
 
+// The same node sums on the open subdivided hyper_rectangle (gls_mesh_hyper_rectangle, mask 0; checked by the host,
+// build_slab_map): nbx x nby x nbz bricks on the lexicographic lattice of NX x NY x NZ nodes, bricks in tile-Morton
+// order -- tiles of s^3 bricks (s = 1 << ls, the largest power of two dividing all three counts) lexicographic with
+// tx fastest, Morton inside a tile:
+//   brick = (((bz >> ls) nty + (by >> ls)) ntx + (bx >> ls)) << 3 ls | morton3(bx & (s-1), by & (s-1), bz & (s-1)).
+// Everything else is k_slab_sum_cube's: a thread's node from (plane, index), per axis the one or two bricks holding
+// it, slot = brick NBND + bnd_index, the sorting network and the ascending-slot sum (bitwise the CSR map's sums).
+__device__ __forceinline__ int64_t morton3_box(uint32_t x, uint32_t y, uint32_t z) {
+  int64_t m = 0;
+  for (int b = 0; b < 11; ++b)
+    m |= ((int64_t)((x >> b) & 1u) << (3 * b)) | ((int64_t)((y >> b) & 1u) << (3 * b + 1)) |
+         ((int64_t)((z >> b) & 1u) << (3 * b + 2));
+  return m;
+}
+template <typename S, bool J, int K>
+__global__ void __launch_bounds__(256) k_slab_sum_box(const S *__restrict__ slab, int nbx, int nby, int nbz, int ls,
+                                                      int64_t voff, double *__restrict__ y,
+                                                      const uint8_t *__restrict__ vmask, const double *__restrict__ jb,
+                                                      const double *__restrict__ jd, double jomega,
+                                                      const double *__restrict__ rb, double *__restrict__ x0) {
+  constexpr int BN = 2 * K + 1, P2 = 2 * K, NBND = BN * BN * BN - (BN - 2) * (BN - 2) * (BN - 2);
+  const int NX = P2 * nbx + 1, NY = P2 * nby + 1;
+  int bx = blockIdx.x, Z = blockIdx.y;
+  if (GLS_SLAB_XCD) {  // XCD-aware: each XCD walks a contiguous range of planes
+    const int lin = xcd_swizzle((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * gridDim.y));
+    bx = lin % (int)gridDim.x;
+    Z = lin / (int)gridDim.x;
+  }
+  const bool zs = Z % P2 == 0;
+  const int64_t t = (int64_t)bx * blockDim.x + threadIdx.x;
+  // surface nodes of plane Z: all of it when Z is a brick boundary, else the full rows Y % 2K == 0
+  // followed by the brick-boundary columns X % 2K == 0 of the other rows
+  int X, Y;
+  const int nsx = nbx + 1, nsy = nby + 1;  // brick-boundary coordinates per axis
+  if (zs) {
+    if (t >= (int64_t)NX * NY) return;
+    X = (int)(t % NX);
+    Y = (int)(t / NX);
+  } else {
+    const int64_t full = (int64_t)nsy * NX, sparse = (int64_t)(NY - nsy) * nsx;
+    if (t >= full + sparse) return;
+    if (t < full) {
+      X = (int)(t % NX);
+      Y = (int)(t / NX) * P2;
+    } else {
+      const int64_t u = t - full;
+      const int r = (int)(u / nsx);  // r-th row that is not a brick boundary
+      X = (int)(u % nsx) * P2;
+      Y = (r / (P2 - 1)) * P2 + 1 + r % (P2 - 1);
+    }
+  }
+  // per axis: (brick coordinate, local coordinate) pairs holding the lattice coordinate
+  int bc[3][2], lc[3][2], nc[3];
+  const int co[3] = {X, Y, Z}, nbd[3] = {nbx, nby, nbz};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const int x = co[d];
+    if (x % P2 == 0 && x > 0 && x < P2 * nbd[d]) {
+      nc[d] = 2;
+      bc[d][0] = x / P2 - 1;
+      lc[d][0] = P2;
+      bc[d][1] = x / P2;
+      lc[d][1] = 0;
+    } else {
+      nc[d] = 1;
+      bc[d][0] = min(x / P2, nbd[d] - 1);
+      lc[d][0] = x - P2 * bc[d][0];
+      bc[d][1] = bc[d][0];
+      lc[d][1] = lc[d][0];
+    }
+  }
+  const int ntx = nbx >> ls, nty = nby >> ls;
+  const uint32_t lm = (1u << ls) - 1u;
+  int64_t sl[8];
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const bool on = i < nc[0] && j < nc[1] && k < nc[2];
+        const int b0 = bc[0][i], b1 = bc[1][j], b2 = bc[2][k];
+        const int64_t tile = ((int64_t)(b2 >> ls) * nty + (b1 >> ls)) * ntx + (b0 >> ls);
+        const int64_t brick = (tile << (3 * ls)) | morton3_box((uint32_t)b0 & lm, (uint32_t)b1 & lm, (uint32_t)b2 & lm);
+        const int64_t s = brick * NBND + bnd_index<BN>(lc[0][i], lc[1][j], lc[2][k]);
+        sl[i + 2 * j + 4 * k] = on ? s : INT64_MAX;
+        cnt += on;
+      }
+  // ascending slot order (sorting network on 8 keys; absent slots sort last)
+  auto cs = [&](int a, int b) {
+    const int64_t lo = min(sl[a], sl[b]), hi = max(sl[a], sl[b]);
+    sl[a] = lo;
+    sl[b] = hi;
+  };
+  cs(0, 1); cs(2, 3); cs(4, 5); cs(6, 7);
+  cs(0, 2); cs(1, 3); cs(4, 6); cs(5, 7);
+  cs(1, 2); cs(5, 6); cs(0, 4); cs(3, 7);
+  cs(1, 5); cs(2, 6);
+  cs(1, 4); cs(3, 6);
+  cs(2, 4); cs(3, 5);
+  cs(3, 4);
+  double e[8][4];
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+    if (q < cnt) SlabQuad<S>::load(slab + sl[q] * 4, e[q][0], e[q][1], e[q][2], e[q][3]);
+  double s[4] = {0., 0., 0., 0.};
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+    if (q < cnt) {
+      s[0] += e[q][0];
+      s[1] += e[q][1];
+      s[2] += e[q][2];
+      s[3] += e[q][3];
+    }
+  const int64_t node = X + (int64_t)NX * (Y + (int64_t)NY * Z);
+  const int64_t gi[4] = {node * 3, node * 3 + 1, node * 3 + 2, voff + node};
+  if constexpr (J) {
+    const unsigned m = vmask ? vmask[node] : 0u;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      const double x = y[gi[f]], dd = jd[gi[f]];
+      y[gi[f]] = x + jomega * (jb[gi[f]] - ((f < 3 && ((m >> f) & 1u)) ? dd * x : s[f])) / dd;
+    }
+  } else if (rb) {
+#pragma unroll
+    for (int f = 0; f < 4; ++f) y[gi[f]] = rb[gi[f]] - s[f];
+    if (x0) {  // the fused first Jacobi sweep's x at this surface node (pencil J.v, OpParams::jx0)
+#pragma unroll
+      for (int f = 0; f < 4; ++f) x0[gi[f]] = 0.0 + jomega * rb[gi[f]] / jd[gi[f]];
+    }
+  } else {
+#pragma unroll
+    for (int f = 0; f < 4; ++f) y[gi[f]] = s[f];
+  }
+}
+hipError_t brick_slab_sum_box(int k, const int nb[3], int s, const double *slab, const float *slabf, int64_t n_vnodes,
+                              double *y, const uint8_t *vmask, const double *jb, const double *jd, double jomega,
+                              hipStream_t st, const double *rb, double *x0) {
+  if (!nb || (k != 1 && k != 2) || s <= 0 || (s & (s - 1)) != 0) return hipErrorInvalidValue;
+  for (int a = 0; a < 3; ++a)
+    if (nb[a] <= 0 || nb[a] > 2048 || nb[a] % s != 0) return hipErrorInvalidValue;
+  if (x0 && (!rb || !jd || jb)) return hipErrorInvalidValue;
+  const int64_t NX = 2 * k * nb[0] + 1, NY = 2 * k * nb[1] + 1, NZ = 2 * k * nb[2] + 1;
+  if (NX * NY * NZ != n_vnodes) return hipErrorInvalidValue;
+  int ls = 0;
+  while ((1 << ls) < s) ++ls;
+  const dim3 g((unsigned)((NX * NY + 255) / 256), (unsigned)NZ), b(256);
+  const int64_t voff = 3 * n_vnodes;
+#define GLS_SLAB_BOX(KK)                                                                                                   \
+  if (slabf) {                                                                                                              \
+    if (jb) hipLaunchKernelGGL((k_slab_sum_box<float, true, KK>), g, b, 0, st, slabf, nb[0], nb[1], nb[2], ls, voff, y, vmask, jb, jd, jomega, rb, x0);  \
+    else hipLaunchKernelGGL((k_slab_sum_box<float, false, KK>), g, b, 0, st, slabf, nb[0], nb[1], nb[2], ls, voff, y, vmask, jb, jd, jomega, rb, x0);   \
+  } else {                                                                                                                  \
+    if (jb) hipLaunchKernelGGL((k_slab_sum_box<double, true, KK>), g, b, 0, st, slab, nb[0], nb[1], nb[2], ls, voff, y, vmask, jb, jd, jomega, rb, x0); \
+    else hipLaunchKernelGGL((k_slab_sum_box<double, false, KK>), g, b, 0, st, slab, nb[0], nb[1], nb[2], ls, voff, y, vmask, jb, jd, jomega, rb, x0);  \
+  }
+  if (k == 1) {
+    GLS_SLAB_BOX(1)
+  } else {
+    GLS_SLAB_BOX(2)
+  }
+#undef GLS_SLAB_BOX
+  return hipGetLastError();
+}
+
 // The V-cycle's restricted residual on the coarse hyper_cube lattice (Q2): a fine brick is one coarse
 // cell, and the pencil J.v (RST) left each brick's residual restricted to that cell's 27 nodes, ev
 // [brick][27][4] in FP64. One thread per coarse node sums its <= 8 entries (two cells per direction

@@ -102,6 +102,11 @@ struct gls_ctx {
   int cube_nb1 = 0;  // > 0: the mesh is the structured hyper_cube with cube_nb1 bricks per direction
                      // (k_slab_sum_cube computes the slab slots from the lattice, the Q2 pencil kernels their
                      // brick nodes' ids, OpParams::cube_gather; GLS_SLAB_CSR=1: off)
+  // > 0: the mesh is the open subdivided hyper_rectangle of gls_mesh_hyper_rectangle, box_nb[a] bricks per axis in
+  // tile-Morton order with tiles of box_s^3 bricks (gls_box_mesh.hpp; verified cell by cell). Read only where
+  // cube_nb1 == 0: k_slab_sum_box computes the slab slots from the lattice. GLS_SLAB_CSR=1: off
+  int box_nb[3] = {0, 0, 0};
+  int box_s = 0;
   // colored brick launches (opt-in GLS_BRICK_COLORS=1): bricks greedily colored in Morton order so
   // that no two bricks of a color share a node (the 2x2x2 parity classes on a brick lattice: 8
   // colors); surface-node sums carried across colors in acc, no slab and no k_slab_sum. Measured

@@ -65,6 +65,11 @@ hipError_t brick_slab_sum_cube(int k, int nb1, const double *slab, const float *
                                const double *rb = nullptr, double *x0 = nullptr,  // x0: OpParams::jx0's surface nodes
                                const double *xs = nullptr);  // xs (k = 2, with jb): the sweep's start values instead
                                                              //   of y's (launch_pencil_jv_prolong's OpParams::pxp)
+// the same sums on the open subdivided hyper_rectangle (nb[a] bricks per axis, lexicographic nodes, bricks in
+// tile-Morton order with tiles of s^3 bricks, s a power of two dividing every nb[a]; gls_box_mesh.hpp)
+hipError_t brick_slab_sum_box(int k, const int nb[3], int s, const double *slab, const float *slabf, int64_t n_vnodes,
+                              double *y, const uint8_t *vmask, const double *jb, const double *jd, double jomega,
+                              hipStream_t st, const double *rb = nullptr, double *x0 = nullptr);
 // coarse right-hand side from the bricks' restricted residuals (launch_pencil_jv_restrict: ev [brick][27][4],
 // nb1 fine bricks = coarse cells per direction): bc[node] = sum of the node's <= 8 element-vector entries in
 // ascending (Morton brick, local node) order, rows in the coarse vmask zeroed; n_vnodes = (2 nb1 + 1)^3.

@@ -853,18 +853,20 @@ static int mg_attach_common(gls_ctx *c, const gls_mg_params *p) {
 }
 
 namespace {
-// nodes per direction of the Qk lattice of an n-cell hyper_cube: a periodic axis has no node of its own at the far face
-std::array<int, 3> wrapped_dims(int n, int K, int mask) {
+// nodes per direction of the Qk lattice of a box of n[a] cells: a periodic axis has no node of its own at the far face
+std::array<int, 3> wrapped_dims(const std::array<int, 3> &n, int K, int mask) {
   std::array<int, 3> d;
-  for (int a = 0; a < 3; ++a) d[a] = K * n + (((mask >> a) & 1) ? 0 : 1);
+  for (int a = 0; a < 3; ++a) d[a] = K * n[a] + (((mask >> a) & 1) ? 0 : 1);
   return d;
 }
-// level g's cells against the lexicographic wrapped lattice dm (the numbering of gls_mesh_hyper_cube with this mask),
+// level g's cells against the lexicographic wrapped lattice dm of n[0] x n[1] x n[2] cells (the numbering of
+// gls_mesh_hyper_cube and gls_mesh_hyper_rectangle with this mask),
 // cell by cell and in any cell order: a cell's first node fixes its origin, a multiple of K per axis, every other node
 // follows modulo the lattice, and no origin is taken twice. nullptr, or what differs
-const char *wrapped_lattice_mismatch(const gls_ctx *g, int n, int K, const std::array<int, 3> &dm, std::vector<int32_t> &cv) {
+const char *wrapped_lattice_mismatch(const gls_ctx *g, const std::array<int, 3> &n, int K, const std::array<int, 3> &dm,
+                                     std::vector<int32_t> &cv) {
   const int K1 = K + 1, N3 = K1 * K1 * K1;
-  if ((int64_t)n * n * n != g->n_cells || (int64_t)dm[0] * dm[1] * dm[2] != g->n_vnodes) return "cell or node count";
+  if ((int64_t)n[0] * n[1] * n[2] != g->n_cells || (int64_t)dm[0] * dm[1] * dm[2] != g->n_vnodes) return "cell or node count";
   if (g->cell_vnodes.n != (size_t)g->n_cells * N3) return "cell node array";
   cv.resize(g->cell_vnodes.n);
   if (hipMemcpy(cv.data(), g->cell_vnodes.p, sizeof(int32_t) * cv.size(), hipMemcpyDeviceToHost) != hipSuccess)
@@ -875,8 +877,8 @@ const char *wrapped_lattice_mismatch(const gls_ctx *g, int n, int K, const std::
     if (v[0] < 0 || v[0] >= g->n_vnodes) return "node out of range";
     const int o[3] = {v[0] % dm[0], (v[0] / dm[0]) % dm[1], v[0] / (dm[0] * dm[1])};
     for (int a = 0; a < 3; ++a)
-      if (o[a] % K != 0 || o[a] / K >= n) return "cell origin off the lattice";
-    uint8_t &sn = seen[(size_t)(((int64_t)(o[2] / K) * n + o[1] / K) * n + o[0] / K)];
+      if (o[a] % K != 0 || o[a] / K >= n[a]) return "cell origin off the lattice";
+    uint8_t &sn = seen[(size_t)(((int64_t)(o[2] / K) * n[1] + o[1] / K) * n[0] + o[0] / K)];
     if (sn) return "two cells at one origin";
     sn = 1;
     for (int e = 1; e < N3; ++e) {
@@ -887,8 +889,9 @@ const char *wrapped_lattice_mismatch(const gls_ctx *g, int n, int K, const std::
   return nullptr;
 }
 
-// gls_mg_attach (mask 0) and gls_mg_attach_periodic
-int mg_attach_nested(gls_ctx *c, const gls_mg_params *p, int mask) {
+// gls_mg_attach (mask 0), gls_mg_attach_periodic and gls_mg_attach_box (cells != nullptr: level l has cells[a] >> l
+// cells on axis a instead of cbrt(n_cells), and every level is checked against its lattice, mask 0 included)
+int mg_attach_nested(gls_ctx *c, const gls_mg_params *p, int mask, const int *cells = nullptr) {
   GLS_TRY(check_ctx(c));
   if (!p || p->n_levels < 2 || !p->levels || p->levels[0] != c) return set_err(GLS_EINVAL, "mg: levels[0] must be ctx");
   if (p->smoother == 3)
@@ -899,7 +902,36 @@ int mg_attach_nested(gls_ctx *c, const gls_mg_params *p, int mask) {
   if (c->map_degree > 0) return set_err(GLS_EINVAL, "mg: nested hyper_cube levels only (not mapped cells)");
   // periodic lattices: every level is checked here, before anything is detached (the context keeps what it had)
   std::vector<std::array<int, 3>> pdims;
-  if (mask) {
+  if (cells) {
+    if (mask < 0 || mask > 7) return set_err(GLS_EINVAL, "mg: periodic_mask has bits 0 - 2 (x, y, z)");
+    if (c->dist.on) return set_err(GLS_EINVAL, "mg: box levels run on one rank (the context is distributed)");
+    std::vector<int32_t> cv;
+    for (int l = 0; l < p->n_levels; ++l) {
+      const gls_ctx *g = p->levels[l];
+      if (!g || g->dim != 3 || g->k != c->k || g->kp != c->kp)
+        return set_err(GLS_EINVAL, "mg level %d: order differs from level 0", l);
+      if (g->dist.on) return set_err(GLS_EINVAL, "mg level %d: box levels run on one rank (the level is distributed)", l);
+      if (g->hang.on || g->map_degree > 0) return set_err(GLS_EINVAL, "mg level %d: hanging nodes or mapped cells", l);
+      std::array<int, 3> n;
+      for (int a = 0; a < 3; ++a) {
+        const bool per = (mask >> a) & 1;
+        if (cells[a] <= 0 || (cells[a] >> l) << l != cells[a])
+          return set_err(GLS_EINVAL, "mg level %d axis %d: %d cells do not halve %d times", l, a, cells[a], l);
+        n[a] = cells[a] >> l;
+        if (n[a] % 2 != 0) return set_err(GLS_EINVAL, "mg level %d axis %d: an odd cell count (%d)", l, a, n[a]);
+        if (n[a] < (per ? 4 : 2))
+          return set_err(GLS_EINVAL, "mg level %d axis %d: %s axis needs at least %d cells (it has %d)", l, a,
+                         per ? "a periodic" : "an open", per ? 4 : 2, n[a]);
+      }
+      if ((int64_t)n[0] * n[1] * n[2] != g->n_cells)
+        return set_err(GLS_EINVAL, "mg level %d not nested (%d cells, %d x %d x %d expected)", l, g->n_cells, n[0], n[1], n[2]);
+      const auto dm = wrapped_dims(n, c->k, mask);
+      if (const char *why = wrapped_lattice_mismatch(g, n, c->k, dm, cv))
+        return set_err(GLS_EINVAL, "mg level %d: its node numbering is not the wrapped lexicographic lattice of the %d x %d x "
+                                   "%d box with periodic mask %d (%s)", l, n[0], n[1], n[2], mask, why);
+      pdims.push_back(dm);
+    }
+  } else if (mask) {
     if (mask < 0 || mask > 7) return set_err(GLS_EINVAL, "mg: periodic_mask has bits 0 - 2 (x, y, z)");
     if (c->dist.on)
       return set_err(GLS_EINVAL, "mg: periodic nested levels run on one rank (periodic_mask %d on a distributed context)", mask);
@@ -914,8 +946,8 @@ int mg_attach_nested(gls_ctx *c, const gls_mg_params *p, int mask) {
       const int n = (int)std::lround(std::cbrt((double)g->n_cells));
       if (n < 2) return set_err(GLS_EINVAL, "mg level %d: a periodic direction needs at least 2 cells (it has %d)", l, n);
       if (l > 0 && nprev != 2 * n) return set_err(GLS_EINVAL, "mg level %d not nested (%d cells per direction below %d)", l, n, nprev);
-      const auto dm = wrapped_dims(n, c->k, mask);
-      if (const char *why = wrapped_lattice_mismatch(g, n, c->k, dm, cv))
+      const auto dm = wrapped_dims({n, n, n}, c->k, mask);
+      if (const char *why = wrapped_lattice_mismatch(g, {n, n, n}, c->k, dm, cv))
         return set_err(GLS_EINVAL, "mg level %d: its node numbering is not the wrapped lexicographic lattice of the "
                                    "hyper_cube with periodic mask %d (%s)", l, mask, why);
       pdims.push_back(dm);
@@ -931,7 +963,7 @@ int mg_attach_nested(gls_ctx *c, const gls_mg_params *p, int mask) {
     if (!g || g->dim != 3 || g->k != c->k || g->kp != c->kp || g->dist.on != mg.boxed)
       return set_err(GLS_EINVAL, "mg level %d: order / distribution differs from level 0", l);
     std::array<int, 3> dm;
-    if (mask) {
+    if (!pdims.empty()) {
       dm = pdims[(size_t)l];
     } else if (mg.boxed) {
       if (!g->lat.set) return set_err(GLS_EINVAL, "mg level %d: distributed level without gls_set_lattice", l);
@@ -962,7 +994,8 @@ int mg_attach_nested(gls_ctx *c, const gls_mg_params *p, int mask) {
   for (int l = 0; l + 1 < p->n_levels; ++l) {
     std::unique_ptr<gls_ctx::MG::Taps> T(new gls_ctx::MG::Taps);
     T->two_pass = true;
-    T->q2_brick = K == 2 && mask == 0;  // the fused transfers' closed form is the open lattice's (nf = 2 nc - 1)
+    // the fused transfers' closed form is the open cube's (nf = 2 nc - 1, Morton bricks)
+    T->q2_brick = K == 2 && mask == 0 && (!cells || (cells[0] == cells[1] && cells[1] == cells[2]));
     T->wrap = mask != 0;
     xwork =std::max(xwork, (size_t)4 * mg.dims[l + 1][0] * mg.dims[l + 1][1] * mg.dims[l][2]);
     for (int a = 0; a < 3; ++a) {
@@ -1038,6 +1071,11 @@ int gls_mg_attach(gls_ctx *c, const gls_mg_params *p) { return mg_attach_nested(
 
 int gls_mg_attach_periodic(gls_ctx *c, const gls_mg_params *p, int periodic_mask) {
   return mg_attach_nested(c, p, periodic_mask);
+}
+
+int gls_mg_attach_box(gls_ctx *c, const gls_mg_params *p, const int cells[3], int periodic_mask) {
+  if (!cells) return set_err(GLS_EINVAL, "gls_mg_attach_box: cells is null");
+  return mg_attach_nested(c, p, periodic_mask, cells);
 }
 
 int gls_mg_attach_transfers(gls_ctx *c, const gls_mg_params *p, const int64_t *const *p_off, const int32_t *const *p_col,

@@ -28,7 +28,8 @@ EXPORTS = [
     "gls_jacobian_apply_f32",
     "gls_jacobian_diagonal", "gls_set_dirichlet", "gls_apply_dirichlet", "gls_solve_linear", "gls_newton_solve",
     "gls_bdf_coefficients", "gls_sdirk_coefficients", "gls_newton_selftest", "gls_mesh_hyper_cube_sizes",
-    "gls_mesh_hyper_cube", "gls_timing_reset", "gls_timing_get", "gls_timing_enable", "gls_uses_brick_kernels",
+    "gls_mesh_hyper_cube", "gls_mesh_hyper_rectangle_sizes", "gls_mesh_hyper_rectangle", "gls_mg_attach_box", "gls_slab_lattice",
+    "gls_timing_reset", "gls_timing_get", "gls_timing_enable", "gls_uses_brick_kernels",
     "gls_part_create", "gls_part_sizes", "gls_part_get", "gls_part_destroy", "gls_dist_attach", "gls_dist_import", "gls_rccl_unique_id", "gls_rccl_create", "gls_rccl_destroy", "gls_rccl_info", "gls_mg_smoother_apply", "gls_mg_attach_replica",
     "gls_dist_attach_rccl",
     "gls_mg_attach", "gls_mg_attach_periodic", "gls_mg_detach", "gls_mg_set_coarse_replica", "gls_residual_and_diagonal", "gls_octree_set_periodic", "gls_ilu_attach", "gls_ilu_detach", "gls_ilu_info", "gls_ilu_matrix", "gls_ilu_factors", "gls_ilu_set_options", "gls_iluk_pattern", "gls_ilu_plan", "gls_cuthill_mckee", "gls_section_timing", "gls_section_get", "gls_dist_attach_dofs", "gls_dist_attach_dofs_rccl", "gls_gpart_create", "gls_gpart_sizes", "gls_gpart_get", "gls_gpart_map_dofs", "gls_gpart_destroy", "gls_dpart_create", "gls_set_lattice", "gls_apply_preconditioner", "gls_mg_transfer",
@@ -188,8 +189,14 @@ def load():
     L.gls_timing_get.argtypes = [vp, C.c_int, d, C.POINTER(i64)]
     L.gls_timing_enable.argtypes = [vp, C.c_int]
     L.gls_uses_brick_kernels.argtypes = [vp]
+    L.gls_slab_lattice.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.gls_mg_attach.argtypes = [vp, C.POINTER(MGParams)]
     L.gls_mg_attach_periodic.argtypes = [vp, C.POINTER(MGParams), C.c_int]
+    L.gls_mg_attach_box.argtypes = [vp, C.POINTER(MGParams), C.POINTER(C.c_int), C.c_int]
+    L.gls_mesh_hyper_rectangle_sizes.argtypes = [C.c_int, C.POINTER(C.c_int)] + [C.c_int] * 3 + [C.POINTER(i64)] * 3
+    L.gls_mesh_hyper_rectangle.argtypes = [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.gls_mg_detach.argtypes = [vp]
     L.gls_mg_set_coarse_replica.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.gls_mg_attach_transfers.argtypes = [vp, C.POINTER(MGParams), C.POINTER(C.POINTER(i64)),
@@ -410,6 +417,32 @@ def hyper_cube(dim, n, k, kp=None, lo=-1.0, hi=1.0, periodic=()):
                                 cp.ctypes.data_as(C.POINTER(C.c_int32)), _dp(x0), _dp(h)), "gls_mesh_hyper_cube")
     return dict(dim=dim, k=k, kp=kp, n_cells=nc, n_vnodes=nv, n_pnodes=npn, cell_vnodes=cv, cell_pnodes=cp,
                 cell_x0=x0, cell_h=h)
+
+
+def mesh_hyper_rectangle(cells, p1, p2, k, kp=None, periodic_mask=0, dim=3):
+    """GridGenerator::subdivided_hyper_rectangle + refine_global through the C++ mesh builder
+    (gls_mesh_hyper_rectangle): cells[a] cells (even) on axis a of the box p1 .. p2, lexicographic nodes, 2 x 2 x 2
+    bricks in tile-Morton order. The dictionary of hyper_cube, with cells, p1, p2 and periodic_mask added."""
+    kp = k if kp is None else kp
+    L = load()
+    cl = (C.c_int * 3)(*[int(v) for v in cells])
+    a1 = (C.c_double * 3)(*[float(v) for v in p1])
+    a2 = (C.c_double * 3)(*[float(v) for v in p2])
+    pm = int(periodic_mask)
+    nc, nv, npn = C.c_int64(), C.c_int64(), C.c_int64()
+    check(L.gls_mesh_hyper_rectangle_sizes(dim, cl, k, kp, pm, C.byref(nc), C.byref(nv), C.byref(npn)),
+          "gls_mesh_hyper_rectangle_sizes")
+    nc, nv, npn = nc.value, nv.value, npn.value
+    cv = np.zeros((nc, (k + 1) ** 3), dtype=np.int32)
+    cp = np.zeros((nc, (kp + 1) ** 3), dtype=np.int32)
+    x0 = np.zeros((nc, 3))
+    h = np.zeros((nc, 3))
+    check(L.gls_mesh_hyper_rectangle(dim, cl, k, kp, a1, a2, pm, cv.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     cp.ctypes.data_as(C.POINTER(C.c_int32)), _dp(x0), _dp(h)),
+          "gls_mesh_hyper_rectangle")
+    return dict(dim=3, k=k, kp=kp, n_cells=nc, n_vnodes=nv, n_pnodes=npn, cell_vnodes=cv, cell_pnodes=cp,
+                cell_x0=x0, cell_h=h, cells=tuple(int(v) for v in cells), p1=tuple(float(v) for v in p1),
+                p2=tuple(float(v) for v in p2), periodic_mask=pm)
 
 
 def refined_cube(dim, n, k, kp=None, refine=None, lo=-1.0, hi=1.0):
@@ -771,6 +804,13 @@ class GLSContext:
     def uses_brick_kernels(self):
         return bool(self.L.gls_uses_brick_kernels(self.h))
 
+    def slab_lattice(self):
+        """(kind, nb, tile) of gls_slab_lattice: kind 0 the index map, 1 the hyper_cube's closed form, 2 the
+        subdivided hyper_rectangle's; nb the bricks per axis and tile the bricks per tile edge (None for kind 0)"""
+        nb, tile = (C.c_int * 3)(), C.c_int()
+        kind = self.L.gls_slab_lattice(self.h, nb, C.byref(tile))
+        return (kind, tuple(nb), tile.value) if kind else (0, None, None)
+
     def zeros(self):
         import torch
         return torch.zeros(self.n_dofs, dtype=torch.float64, device="cuda")
@@ -881,14 +921,16 @@ class GLSContext:
 
     def attach_multigrid(self, coarse_levels, pre_smooth=2, post_smooth=2, coarse_sweeps=30, omega=0.6,
                          coarse_omega=0.0, coarse_direct=0, mixed_precision=0, level_sweeps=None, smoother_operator=0,
-                         periodic=None):
+                         periodic=None, box=None):
         """GMRES right preconditioner = geometric multigrid V-cycle over [self] + coarse_levels
         (GLSContext objects of the same problem on hyper_cube(n/2^l)). Keeps references alive.
         level_sweeps: optional {level: (pre, post)} overriding pre_smooth / post_smooth per level
         (negative level indices count from the coarsest). smoother_operator=1: the FP32 smoothing J.v
         applies the Oseen (Picard) linearization (gls_mg_params.smoother_operator). periodic: the periodic
         directions of the levels' hyper_cubes, through gls_mg_attach_periodic (an empty tuple is its mask 0, which is
-        gls_mg_attach; None calls gls_mg_attach itself)."""
+        gls_mg_attach; None calls gls_mg_attach itself). box=(cells, periodic): the levels are subdivided
+        hyper_rectangles of cells[a] >> l cells per axis with the periodic directions given, through
+        gls_mg_attach_box."""
         levels = [self] + list(coarse_levels)
         arr = (C.c_void_p * len(levels))(*[lv.h for lv in levels])
         ls = None
@@ -901,7 +943,15 @@ class GLSContext:
             ls = (C.c_int * len(flat))(*flat)
         p = MGParams(len(levels), C.cast(arr, C.POINTER(C.c_void_p)), pre_smooth, post_smooth, coarse_sweeps, omega,
                      coarse_omega, coarse_direct, int(mixed_precision), ls, 0, int(smoother_operator))
-        if periodic is not None:
+        if box is not None and periodic is not None:
+            raise ValueError("attach_multigrid: box=(cells, periodic) carries the periodic directions; do not pass "
+                             "periodic= with it")
+        if box is not None:
+            cells, per = box
+            pm = sum(1 << d for d in set(per))
+            check(self.L.gls_mg_attach_box(self.h, C.byref(p), (C.c_int * 3)(*[int(v) for v in cells]), pm),
+                  "gls_mg_attach_box")
+        elif periodic is not None:
             pm = sum(1 << d for d in set(periodic))
             check(self.L.gls_mg_attach_periodic(self.h, C.byref(p), pm), "gls_mg_attach_periodic")
         else:

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .native import GLSContext, hyper_cube
+from .native import GLSContext, hyper_cube, mesh_hyper_rectangle
 
 
 def vnode_boundary_ids(mesh, n, lo, hi, colorize):
@@ -130,7 +130,9 @@ class PeriodicBoxProblem:
             while m % 2 == 0 and m // 2 >= mg_coarsest:
                 m //= 2
                 self.levels.append(PeriodicBoxProblem(m, k, self.periodic, lo, hi, viscosity, stream))
-            self.ctx.attach_multigrid([lv.ctx for lv in self.levels], periodic=self.periodic, **mg_opts)
+            if "box" not in mg_opts:  # box=(cells, periodic) carries the directions itself (gls_mg_attach_box)
+                mg_opts = dict(mg_opts, periodic=self.periodic)
+            self.ctx.attach_multigrid([lv.ctx for lv in self.levels], **mg_opts)
 
     def taylor_green(self, t=0.0):
         """the Taylor-Green vortex at the nodes (the initial condition of apps/cases/tgv3d_*.prm) with amplitude
@@ -142,6 +144,45 @@ class PeriodicBoxProblem:
         u = np.concatenate([vel.reshape(-1), p])
         u[self.dir_dofs] = self.dir_vals
         return u
+
+
+class BoxProblem:
+    """3D subdivided hyper_rectangle p1 .. p2 with cells[a] cells (even) on axis a, the directions in `periodic`
+    identified and no-slip walls on the faces of the others (mesh_hyper_rectangle: lexicographic wrapped node lattice,
+    bricks in tile-Morton order; `coords` holds the node positions). multigrid=True: nested levels cells / 2,
+    cells / 4, ... while every count stays even, at least mg_coarsest and at least 2 (4 on a periodic axis), each
+    with its own Dirichlet list, attached through gls_mg_attach_box."""
+
+    def __init__(self, cells, p1, p2, k=2, periodic=(), viscosity=0.01, stream=None, multigrid=False, mg_coarsest=2,
+                 **mg_opts):
+        self.dim, self.k, self.kp = 3, k, k
+        self.cells, self.periodic = tuple(int(c) for c in cells), tuple(sorted(set(periodic)))
+        self.p1, self.p2 = np.asarray(p1, dtype=float), np.asarray(p2, dtype=float)
+        pm = sum(1 << d for d in self.periodic)
+        self.mesh = mesh_hyper_rectangle(self.cells, self.p1, self.p2, k, k, pm)
+        self.shape = [k * self.cells[d] if d in self.periodic else k * self.cells[d] + 1 for d in range(3)]
+        idx = np.indices(self.shape[::-1]).reshape(3, -1)[::-1].T  # lexicographic, x fastest
+        self.coords = self.p1 + idx * ((self.p2 - self.p1) / (k * np.asarray(self.cells)))
+        wall = np.zeros(idx.shape[0], dtype=bool)
+        for d in range(3):
+            if d not in self.periodic:
+                wall |= (idx[:, d] == 0) | (idx[:, d] == self.shape[d] - 1)
+        self.vnode_mask = np.where(wall, 7, 0).astype(np.uint8)
+        nodes = np.nonzero(wall)[0]
+        self.dir_dofs = (nodes[:, None] * 3 + np.arange(3)[None]).reshape(-1).astype(np.int64)
+        self.dir_vals = np.zeros(self.dir_dofs.size)
+        self.ctx = build_context(self.mesh, viscosity=viscosity, vnode_mask=self.vnode_mask, stream=stream)
+        if self.dir_dofs.size:
+            self.ctx.set_dirichlet(self.dir_dofs, self.dir_vals)
+        self.n_dofs = self.ctx.n_dofs
+        self.levels = []
+        if multigrid:
+            m = self.cells
+            floor = [max(mg_coarsest, 4 if d in self.periodic else 2) for d in range(3)]
+            while all(c % 4 == 0 and c // 2 >= f for c, f in zip(m, floor)):
+                m = tuple(c // 2 for c in m)
+                self.levels.append(BoxProblem(m, p1, p2, k, self.periodic, viscosity, stream))
+            self.ctx.attach_multigrid([lv.ctx for lv in self.levels], box=(self.cells, self.periodic), **mg_opts)
 
 
 def octree_lid_tree(n=4, steps=3, dim=3, base=2):
